@@ -1,7 +1,14 @@
 """Benchmark: nodes ranked/s of the fit-and-rank path on MI355X, through the drop-in API.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4|cfg1|cfg2|cfg3|cfg5]
-                    [--mode auto|replicas|partitioned] [--no-cpu-baseline] [--cpu-sample N]
+                    [--mode auto|api|partitioned] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--cpu-sample N] [--resident-steps R]]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--dump-outputs
+DIR`` also writes what the last timed step returned (distance tables and Borda ranks, float64,
+``DIR/<name>.npy``; the same seeded row sample of every array when they exceed 48 MB together).
+The inputs are seeded, so two builds can be compared output for output.  ``--full`` adds the
+legs listed under "Extra keys" and the torchrun side legs.
 
 One step = what a caller of the reference does: from host-resident
 scipy CSR layers (dense fp32 arrays for cfg3), ``N2V2R(graphs, nodes, config)`` +
@@ -12,7 +19,7 @@ copies, the DataFrames and the Borda of the frames.  ``value`` = nodes ranked/s 
 comparisons x steps / max-over-ranks wall time.  Default workload: BASELINE cfg4 (2-layer ER
 N=1M avg-deg 50, 10-column grid), the largest configuration that fits one GPU.
 
-Extra keys:
+Extra keys (``--full`` only):
   * ``device_resident``: the same work with the layers already in HBM (engine-level loop: UASE,
     distances, Borda, copies of the tables to the host), for comparison;
   * ``roofline``: the dominant kernel of the fit (the SpMM stage launch that takes the most
@@ -30,7 +37,8 @@ Multi-GPU, --gpus N > 1 (cfg1-4; with or without torchrun): the headline is the 
 API call on ONE graph of the workload, row-partitioned over N GPUs by the library itself
 (``N2V2R(..., devices=[0..N-1])``: one host thread per GPU inside libn2v2r_hip.so, RCCL over
 the N devices), "scaling": "strong".  Under torchrun (the driver's launcher)
-rank 0 makes that call and the other ranks wait at the barriers; they then join the side legs:
+rank 0 makes that call and the other ranks wait at the barriers; with ``--full`` they then join
+the side legs:
 ``replicas`` (every rank its own graph through the API on its own GPU, weak scaling) and
 ``partitioned_per_process`` (one graph row-partitioned over one process per GPU, RCCL between
 processes).  cfg5 (or --mode partitioned) runs one row-partitioned graph with every rank
@@ -399,6 +407,44 @@ def replicas_leg(group, cfg, args, local, rank, world):
                      "GPU (one process per GPU)"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files together (at most 64 MB asked for)
+DUMP_SAMPLE_SEED = 20240229
+
+
+def step_outputs(res, mode):
+    """What a caller of the timed path receives from one step, as named float64 arrays with the
+    nodes along axis 0: per comparison key the N x C distance table and the N Borda ranks."""
+    out = {}
+    if mode == "partitioned":
+        for c, (D, b) in enumerate(res[1]):
+            out[f"distances_{c + 1}"] = np.asarray(D, dtype=np.float64)
+            out[f"borda_ranks_{c + 1}"] = np.asarray(b, dtype=np.float64)
+    else:
+        _, ranks, agg = res
+        for key, df in ranks.items():
+            out[f"distances_{key}"] = df.to_numpy(dtype=np.float64)
+        for key, df in agg.items():
+            out[f"borda_ranks_{key}"] = df.to_numpy(dtype=np.float64)[:, 0]
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy.  Outputs over DUMP_BUDGET_BYTES are cut to the same
+    rows of every array: a sorted sample drawn with a fixed seed, stored as sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = min(a.shape[0] for a in arrays.values())
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in arrays.values()) + 8
+    keep = DUMP_BUDGET_BYTES // row_bytes
+    rows = None
+    if keep < n:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        rows = np.sort(rng.choice(n, size=keep, replace=False))
+        np.save(os.path.join(path, "sample_rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(a if rows is None else a[rows]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -409,7 +455,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="faithful sample N override")
     ap.add_argument("--resident-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: device-resident loop, "
+                         "instrumented roofline fit, torchrun side legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # a progress line on stderr every 45 s (long configurations: cfg5's synthesis and ingest
     # print nothing for minutes)
@@ -523,13 +576,16 @@ def main():
             ncmp = len(res[1])
             stats = res[0].eig_stats
     value = nodes_per_step * ncmp * args.steps / elapsed_max
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(res, mode))
 
-    # device-resident form of the same work (layers already in HBM), and one instrumented fit
-    # for the roofline (HIP events around every SpMM launch; rank 0's launches on N GPUs)
+    # --full: device-resident form of the same work (layers already in HBM), and one instrumented
+    # fit for the roofline (HIP events around every SpMM launch; rank 0's launches on N GPUs)
     res_ms = None
     roof = None
+    reng = None
     st_t = {}
-    if active:
+    if active and args.full:
         if mode == "partitioned":
             reng = eng
         else:
@@ -608,7 +664,8 @@ def main():
     result = {
         "metric": BASELINE_METRIC,
         "metric_detail": "nodes ranked/sec (fit_transform_rank + aggregate_transform, host CSR "
-                         "in, host DataFrames out); the SpMM GB/s half is roofline.achieved",
+                         "in, host DataFrames out); the SpMM GB/s half is roofline.achieved "
+                         "(--full)",
         "value": round(value, 1),
         "unit": "nodes/s",
         "n_gpus": n_gpus,
@@ -628,7 +685,8 @@ def main():
                                   if mode == "partitioned" else
                                   "host CSR -> N2V2R -> fit_transform_rank -> "
                                   "aggregate_transform -> host DataFrames (H2D included)")},
-        "roofline": roof,
+        "full": args.full,
+        "roofline": roof,  # (--full only, like device_resident, the side legs and cpu_baseline)
         # solver counters of the timed fit (ms_spmm / ms_ortho are host-side launch times of
         # asynchronous work, so they are left out; the device time is in roofline)
         "eig": {k: (float(f"{v:.4g}") if isinstance(v, float) else v)
@@ -641,7 +699,7 @@ def main():
     # torchrun at N > 1: side legs beside the headline, each under a watchdog (rank 0 prints the
     # line with a leg marked as timed out and every rank exits with WATCHDOG_EXIT) --
     # N2V2R_BENCH_SIDE=0 skips them
-    if (world > 1 and mode == "api" and not cfg.get("dense")
+    if (args.full and world > 1 and mode == "api" and not cfg.get("dense")
             and os.environ.get("N2V2R_BENCH_SIDE", "1") != "0"):
         limit = float(os.environ.get("N2V2R_BENCH_SIDE_S", "300"))
         legs = [("replicas", replicas_leg)]
@@ -660,7 +718,7 @@ def main():
                     return {"error": repr(e)[:300]}
 
             result[key] = run_guarded(_leg, limit, _expire)
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         avail, how = host_cpus()
         # the reference's pool: joblib n_jobs=-2 = all CPUs but one (model_utils.py:31-32)
         workers = max(1, avail - 1)
@@ -672,7 +730,7 @@ def main():
         print(json.dumps(result), flush=True)
     if eng is not None:
         eng.close()
-    elif active:
+    elif reng is not None:
         reng.close()
     group.close()
 

@@ -3,7 +3,7 @@
 #   bash tools/gpu/steps.sh OUTDIR STEP [STEP ...]
 # Steps (each GPU step under its own time limit; the first failure ends the script):
 #   tests         the whole GPU suite (pytest -m gpu) + __graft_entry__.smoke()
-#   bench:CFG     one bench.py line for cfg1 / cfg2 / cfg3 / cfg4 (5 steps) or cfg5 (2 steps)
+#   bench:CFG     one bench.py --full line for cfg1 / cfg2 / cfg3 / cfg4 (5 steps) or cfg5 (2 steps)
 #   kt:CFG        rocprofv3 kernel trace + stats of one bench step of CFG
 #   pmc4          the cfg4 tiled SpMM's counter passes (FETCH_SIZE, WRITE_SIZE, fabric read
 #                 requests + L2 hits / misses), each pass a run of its own
@@ -28,7 +28,7 @@ prof() {  # prof NAME LIMIT rocprofv3-args... (the program directly after --)
   timeout -k 10 "$lim" rocprofv3 "$@" > "$O/$name.log" 2>&1 || fail "$name" $? "$O/$name.log"
 }
 bench_args() {  # the bench command line of one step of CFG, no CPU baseline
-  echo "bench.py --config $1 --steps 1 --warmup 1 --resident-steps 0 --no-cpu-baseline"
+  echo "bench.py --config $1 --steps 1 --warmup 1 --full --resident-steps 0 --no-cpu-baseline"
 }
 
 for step in "$@"; do
@@ -41,12 +41,12 @@ for step in "$@"; do
         > "$O/smoke.log" 2>&1 || fail smoke $? "$O/smoke.log"
       ;;
     bench:cfg5)
-      timeout -k 10 600 python -u bench.py --config cfg5 --steps 2 --warmup 1 --resident-steps 1 \
+      timeout -k 10 600 python -u bench.py --config cfg5 --steps 2 --warmup 1 --full --resident-steps 1 \
         > "$O/bench_cfg5.json" 2> "$O/bench_cfg5.err" || fail "bench cfg5" $? "$O/bench_cfg5.err"
       ;;
     bench:*)
       c=${step#bench:}
-      timeout -k 10 400 python -u bench.py --config "$c" --steps 5 --warmup 2 \
+      timeout -k 10 400 python -u bench.py --config "$c" --steps 5 --warmup 2 --full \
         > "$O/bench_$c.json" 2> "$O/bench_$c.err" || fail "bench $c" $? "$O/bench_$c.err"
       ;;
     kt:*)
