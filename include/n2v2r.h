@@ -198,6 +198,24 @@ int n2v2r_set_layer_csr(n2v2r_handle* h, int k, int64_t n, int64_t nnz, const in
  * application becomes dense MFMA GEMMs.  All layers of a handle are CSR or all dense.
  * symmetric: N2V2R_SYM_* (DETECT compares A with A^T on the GPU). */
 int n2v2r_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int symmetric);
+/* co-expression layer built on the GPU from its expression matrix: E row-major n x samples fp64
+ * on the host (n nodes / genes).  The layer is t(r), r = the Pearson correlation of the rows of E
+ * as np.corrcoef(E) gives it (clipped to [-1, 1]): every row is centred by its two-pass mean and
+ * divided by its centred 2-norm in fp64, r = Z Z^T by fp64 MFMA, and per entry, still in fp64,
+ *   t = |r| (N2V2R_CORR_UNSIGNED), (1 + r) / 2 (N2V2R_CORR_SIGNED), max(r, 0)
+ *   (N2V2R_CORR_SIGNED_HYBRID) or r (N2V2R_CORR_RAW), then t = pow(t, power) when power != 1,
+ * rounded once to fp32; the diagonal is exactly 1 and the layer bit-exactly symmetric.  It is
+ * stored as n2v2r_set_layer_dense stores a symmetric layer (this rank's rows; the "all CSR or all
+ * dense" rule applies) and no n x n array exists on the host: the upload is 8 n samples bytes
+ * (every rank of a partitioned handle uploads E whole and builds its own rows, the same bits one
+ * GPU builds).  N2V2R_ERR_BAD_ARG: samples < 2, an unknown kind, power not finite or < 1,
+ * power != 1 with N2V2R_CORR_RAW, or a row of E that holds a non-finite value or is constant (the
+ * message names the smallest such row); the layer is then not loaded and the call can be
+ * repeated. */
+enum { N2V2R_CORR_UNSIGNED = 0, N2V2R_CORR_SIGNED = 1, N2V2R_CORR_SIGNED_HYBRID = 2,
+       N2V2R_CORR_RAW = 3 };
+int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples,
+                         const double* E /* n x samples, row-major */, int kind, double power);
 /* distributed ingest without the global CSR on every rank: the caller's own rows
  * [row0, row0 + n_rows) (must equal n2v2r_dist_info's) of a SYMMETRIC layer, indptr local
  * (starting at 0), column indices global. */

@@ -47,10 +47,17 @@ int n2v2r_rr_band_top(n2v2r_handle* h, int c, int kp, const double* hband, int64
                       const double* theta_prev, int p, double* w, float* S);
 
 /* Layer bytes each rank copied host -> device so far (one-GPU handle: one entry): row pointers,
- * column indices and values of every layer ingest, into per_rank[0 .. min(W, cap)).  Returns the
+ * column indices and values of every CSR layer ingest and the 8 n samples bytes of every
+ * n2v2r_set_layer_corr (each rank uploads E whole), into per_rank[0 .. min(W, cap)).  Returns the
  * rank count W.  A multi-GPU handle slices layers on the host, so each rank's figure is about
  * 1/W of the layers' bytes (2/W for directed layers: rows of A and of A^T). */
 int n2v2r_h2d_layer_bytes(const n2v2r_handle* h, int64_t* per_rank, int cap);
+
+/* A dense layer (n2v2r_set_layer_dense, n2v2r_set_layer_corr) copied back to the host: A is
+ * row-major n x n fp32.  A multi-GPU handle returns all N rows; a rank handle writes its local
+ * rows at their global offset (rows [row0, row0 + n_local) of A) and leaves the rest alone.
+ * N2V2R_ERR_BAD_ARG when layer k is not a loaded dense layer. */
+int n2v2r_get_layer_dense(n2v2r_handle* h, int k, float* A /* n x n */);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,8 @@ import weakref
 
 import numpy as np
 
+from .coexpression import Coexpression
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("N2V2R_LIB", os.path.join(_HERE, "lib", "libn2v2r_hip.so"))
 
@@ -51,6 +53,7 @@ EXPORTED = [
     "n2v2r_simgroup_destroy", "n2v2r_create_sim", "n2v2r_dist_info", "n2v2r_set_layer_csr_rows",
     "n2v2r_rr_top", "n2v2r_rr_band_top", "n2v2r_set_layer_dense", "n2v2r_project",
     "n2v2r_create_multi", "n2v2r_multi_devices", "n2v2r_h2d_layer_bytes",
+    "n2v2r_set_layer_corr", "n2v2r_get_layer_dense",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -165,6 +168,9 @@ def load(path: str | None = None):
             "n2v2r_create_multi": (_i, [_p(np.int32), _i, ctypes.POINTER(_vp)]),
             "n2v2r_multi_devices": (_i, [_vp, _vp, _i]),
             "n2v2r_h2d_layer_bytes": (_i, [_vp, _vp, _i]),
+            "n2v2r_set_layer_corr": (_i, [_vp, _i, _i64, _i64, _p(np.float64), _i,
+                                          ctypes.c_double]),
+            "n2v2r_get_layer_dense": (_i, [_vp, _i, _p(np.float32)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -338,11 +344,42 @@ class Engine:
 
     # -- layers ----------------------------------------------------------------------------
     def set_layers(self, layers, symmetric=SYM_DETECT, storage="auto"):
-        """layers: list of scipy.sparse matrices (any format) or dense arrays, N x N.
+        """layers: list of scipy.sparse matrices (any format) or dense arrays, N x N, or
+        ``Coexpression`` layers (an N x samples expression matrix each: the engine builds the
+        N x N co-expression layer on the GPU, n2v2r_set_layer_corr).
 
         storage: "csr", "dense" (fp32 N x N in HBM, MFMA GEMMs) or "auto" (dense when every
-        layer is a dense array with more than 1/4 of its entries non-zero)."""
+        layer is a dense array with more than 1/4 of its entries non-zero).  A list that holds a
+        ``Coexpression`` is dense storage: its other layers must be dense arrays."""
         import scipy.sparse as sp
+        corr = [isinstance(a, Coexpression) for a in layers]
+        if any(corr):
+            # (every check before the first library call: a refused list leaves the handle as is)
+            if storage == "csr":
+                raise ValueError("Coexpression layers are stored dense: storage='csr' does not "
+                                 "apply")
+            if any(sp.issparse(a) for a in layers):
+                raise ValueError("a sparse layer cannot share a handle with Coexpression layers "
+                                 "(all layers of a handle are CSR or all dense): pass it as a "
+                                 "dense array")
+            arrs = [a if c else np.ascontiguousarray(np.asarray(a), dtype=np.float32)
+                    for a, c in zip(layers, corr)]
+            n = arrs[0].shape[0]
+            for a in arrs:
+                if a.shape != (n, n):
+                    raise ValueError("all layers must be square and share the node set")
+            self._check(self.lib.n2v2r_set_num_layers(self.h, len(arrs), n), "set_num_layers")
+            for k, a in enumerate(arrs):
+                if isinstance(a, Coexpression):
+                    st = self.lib.n2v2r_set_layer_corr(self.h, k, n, a.expression.shape[1],
+                                                       a.expression, a.kind_id, a.power)
+                else:
+                    st = self.lib.n2v2r_set_layer_dense(self.h, k, n, a, int(symmetric))
+                self._check(st, f"layer {k}")
+            self.n = n
+            self.num_layers = len(arrs)
+            self.storage = "dense"
+            return
         if storage == "auto":
             storage = "csr"
             if all(not sp.issparse(a) for a in layers):
@@ -525,6 +562,13 @@ class Engine:
         out = np.empty(self.n, dtype=np.float32)
         self._check(self.lib.n2v2r_column_sums(self.h, int(k), out), "column_sums")
         return out
+
+    def layer_dense(self, k: int):
+        """Dense layer k back on the host (n2v2r_get_layer_dense): N x N float32.  A rank handle
+        fills its own rows [row0, row0 + n_local) and leaves the others zero."""
+        A = np.zeros((self.n, self.n), dtype=np.float32)
+        self._check(self.lib.n2v2r_get_layer_dense(self.h, int(k), A), "layer_dense")
+        return A
 
     def bench_spmm(self, k: int, X, transpose: bool = False, reps: int = 20, want_y=True):
         """Time the SpMM kernel alone (HIP events on the engine stream)."""

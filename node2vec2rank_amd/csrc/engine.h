@@ -139,6 +139,13 @@ hipError_t n2v2r_launch_dense_gemm(const float* A, int64_t lda, int64_t rows, in
                                    size_t work_elems, hipStream_t stream);
 hipError_t n2v2r_launch_syrk_f64(const double* W, int64_t sk, int64_t si, int64_t kd, int64_t r,
                                  double* out, int64_t ldo, hipStream_t stream);
+// corr.hip: co-expression layers from expression matrices
+int64_t n2v2r_corr_spad(int64_t s);
+hipError_t n2v2r_launch_corr_standardise(const double* E, int64_t n, int64_t s, double* Z,
+                                         unsigned* bad, hipStream_t stream);
+hipError_t n2v2r_launch_corr_tiles(const double* Z, int64_t s, int64_t n, int64_t row0,
+                                   int64_t nloc, float* A, int64_t lda, int kind, double power,
+                                   hipStream_t stream);
 hipError_t n2v2r_launch_transpose(const float* in, int64_t ldi, int64_t rows, int64_t cols,
                                   float* out, int64_t ldo, hipStream_t stream);
 hipError_t n2v2r_launch_mismatch(const float* a, const float* b, int64_t ld, int64_t rows,
@@ -747,6 +754,9 @@ int multi_set_num_layers(n2v2r_handle* h, int num_layers, int64_t n);
 int multi_set_layer_csr(n2v2r_handle* h, int k, int64_t n, int64_t nnz, const int64_t* indptr,
                         const int32_t* indices, const float* data, int symmetric);
 int multi_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int symmetric);
+int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, const double* E,
+                         int kind, double power);
+int multi_get_layer_dense(n2v2r_handle* h, int k, float* A);
 int multi_column_sums(n2v2r_handle* h, int k, float* out);
 int multi_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_stats* stats);
 int multi_get_embedding(n2v2r_handle* h, float* Y);

@@ -586,6 +586,96 @@ int n2v2r_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int
   });
 }
 
+// Co-expression layer from its n x samples expression matrix (corr.hip): E is uploaded whole
+// (8 n samples bytes, on every rank of a partitioned handle), standardised on the GPU, and this
+// rank's rows of t(corrcoef(E)) are written straight into the layer's dA by the fused tile
+// kernel.  The layer counts as not loaded from the first check on until the kernels succeeded.
+int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, const double* E,
+                         int kind, double power) {
+  if (h && h->multi()) return multi_set_layer_corr(h, k, n, samples, E, kind, power);
+  return guarded(h, [&]() -> int {
+    if (k < 0 || k >= h->K || n != h->n || n < 1 || !E) {
+      h->set_err("bad co-expression arguments for layer %d", k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    LayerDev& L = *h->layers[k];
+    L.loaded = false;
+    h->have_embedding = false;
+    if (samples < 2) {
+      h->set_err("layer %d: a correlation needs at least 2 samples, got %lld", k,
+                 (long long)samples);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (kind != N2V2R_CORR_UNSIGNED && kind != N2V2R_CORR_SIGNED &&
+        kind != N2V2R_CORR_SIGNED_HYBRID && kind != N2V2R_CORR_RAW) {
+      h->set_err("layer %d: unknown correlation kind %d", k, kind);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (!std::isfinite(power) || power < 1.0) {
+      h->set_err("layer %d: power must be finite and >= 1, got %g", k, power);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (kind == N2V2R_CORR_RAW && power != 1.0) {
+      h->set_err("layer %d: a raw correlation layer takes power 1 (r may be negative), got %g", k,
+                 power);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    for (int j = 0; j < h->K; ++j)
+      if (j != k && h->layers[j]->loaded && !h->layers[j]->dense) {
+        h->err = "layers must be all CSR or all dense";
+        return N2V2R_ERR_BAD_ARG;
+      }
+    hipStream_t st = h->stream;  // (n <= 2^31 - 1: n2v2r_set_num_layers)
+    const int64_t npad = (n + 63) / 64 * 64, sp = n2v2r_corr_spad(samples);
+    DevBuf e, z;  // (the kernels write every element of z)
+    e.ensure_raw(sizeof(double) * n * samples);
+    z.ensure_raw(sizeof(double) * npad * sp);
+    DevBuf& flag = h->ing_flag;
+    flag.ensure_raw(sizeof(unsigned) * 4);
+    HIPCHK(hipMemcpyAsync(e.p, E, sizeof(double) * n * samples, hipMemcpyHostToDevice, st));
+    h->h2d_layer_bytes += 8 * n * samples;
+    HIPCHK(hipMemsetAsync(flag.p, 0xFF, sizeof(unsigned), st));
+    HIPCHK(n2v2r_launch_corr_standardise(e.as<double>(), n, samples, z.as<double>(),
+                                         flag.as<unsigned>(), st));
+    unsigned bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad != 0xFFFFFFFFu) {
+      h->set_err("layer %d: row %u of the expression matrix holds a non-finite value or is "
+                 "constant (zero variance): its correlations are undefined", k, bad);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    L.dense = true;
+    L.n_rows = h->nloc;
+    L.lda = npad;
+    L.dA.ensure(sizeof(float) * std::max<int64_t>(h->nloc, 1) * L.lda);
+    L.dAT.release();
+    HIPCHK(n2v2r_launch_corr_tiles(z.as<double>(), samples, n, h->row0, h->nloc, L.dA.as<float>(),
+                                   L.lda, kind, power, st));
+    HIPCHK(hipStreamSynchronize(st));  // e and z die here
+    L.symmetric = true;
+    L.loaded = true;
+    return N2V2R_OK;
+  });
+}
+
+// diagnostics (n2v2r_diag.h): a dense layer's rows back on the host
+int n2v2r_get_layer_dense(n2v2r_handle* h, int k, float* A) {
+  if (h && h->multi()) return multi_get_layer_dense(h, k, A);
+  return guarded(h, [&]() -> int {
+    if (k < 0 || k >= h->K || !A || !h->layers[k]->loaded || !h->layers[k]->dense) {
+      h->set_err("get_layer_dense: layer %d is not a loaded dense layer", k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    const LayerDev& L = *h->layers[k];
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->nloc > 0)
+      HIPCHK(hipMemcpy2D(A + h->row0 * h->n, sizeof(float) * h->n, L.dA.p, sizeof(float) * L.lda,
+                         sizeof(float) * h->n, h->nloc, hipMemcpyDeviceToHost));
+    return N2V2R_OK;
+  });
+}
+
 int n2v2r_set_layer_csr_rows(n2v2r_handle* h, int k, int64_t n, int64_t row0, int64_t n_rows,
                              int64_t nnz, const int64_t* indptr, const int32_t* indices,
                              const float* data) {

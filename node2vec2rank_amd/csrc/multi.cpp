@@ -239,6 +239,23 @@ int multi_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int
   return fanout(h, [&](n2v2r_handle* r, int) { return n2v2r_set_layer_dense(r, k, n, A, symmetric); });
 }
 
+// every rank uploads the (small) expression matrix whole and builds its own row band
+int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, const double* E,
+                         int kind, double power) {
+  return fanout(h, [&](n2v2r_handle* r, int) {
+    return n2v2r_set_layer_corr(r, k, n, samples, E, kind, power);
+  });
+}
+
+// rank r's rows land at row0 of the caller's n x n array (disjoint bands)
+int multi_get_layer_dense(n2v2r_handle* h, int k, float* A) {
+  if (!A) {
+    h->err = "get_layer_dense: null output buffer";
+    return N2V2R_ERR_BAD_ARG;
+  }
+  return fanout(h, [&](n2v2r_handle* r, int) { return n2v2r_get_layer_dense(r, k, A); });
+}
+
 int multi_column_sums(n2v2r_handle* h, int k, float* out) {
   // validated here, alike for every rank (rank 0 alone would see a null `out`, and the others
   // would wait for it in the all-gather)

@@ -28,12 +28,16 @@ import pandas as pd
 import scipy.sparse as sp
 
 from . import _lib
+from .coexpression import Coexpression
 
 
 def _as_layer(g):
     """Layers as the engine takes them: scipy sparse stays sparse (CSR), dense arrays and
     DataFrames stay dense (the engine stores them dense in HBM when they are more than 1/4
-    non-zero, CSR otherwise)."""
+    non-zero, CSR otherwise); a ``Coexpression`` (an expression matrix whose network the engine
+    builds on the GPU) passes through."""
+    if isinstance(g, Coexpression):
+        return g
     if isinstance(g, pd.DataFrame):
         g = g.values
     if sp.issparse(g):
