@@ -2250,6 +2250,440 @@ extern "C" hipError_t n2v2r_launch_pip_fused(const BlockList& Q, const float* Zi
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------- paired apply (Eig::pair_pass)
+// The two selective passes of a pair, Za against Q and Zb against [Q Za'], in one read of the
+// basis.  pair_plan_kernel (one workgroup) takes both passes' decisions from the pair's Grams:
+// each pass's block list, P, R and R^{-1} exactly as pip_fused_kernel's prologue takes them
+// (pair_side below is that prologue as a function), and between them Zb's Gram against the
+// corrected Za' exactly as pair_fixup_kernel forms it.  It leaves a plan in global memory:
+//   words [0, 16)   nunion | bit 0: pass a skipped, 1: pass b skipped, 2: b applies Za' |
+//                   bad columns of a | of b
+//   [16, 208)       R_a^{-1}, R_b^{-1}, Zb's coefficients against Za' (8 x 8 fp32 each)
+//   [208, 208 + umax)        the union of the two lists, ascending: block | side mask << 16
+//   then 128 floats per union entry: the block's 8 x 8 coefficients for Za, then for Zb
+// pip_pair_kernel copies the plan to LDS (fp32 only: 33 KB at 512 basis columns against the
+// 50 KB of pip_fused_kernel's fp64 Gram and coefficients) and streams its rows once: a basis
+// block's rows are loaded once and update Za's and Zb's accumulators as the masks say, Za' is
+// finished, Zb takes Za' from registers (the lane that holds a row's column half of Za' is the
+// lane that the second launch would load it with), Zb' is finished, both are stored.  Every
+// output element sees the operations of the two-launch path in the same order.
+#define PAIR_PLAN_HDR 16
+#define PAIR_PLAN_LIST (PAIR_PLAN_HDR + 192)
+
+// One selective pass's prologue on its staged Gram gd ((c + 8) x 8 fp64 in LDS), by all 256
+// threads of the one workgroup: pip_fused_kernel's, statement for statement (first = 0, no
+// cond, no save).  Leaves blist[0, badw[1]), badw[0] = bad columns, badw[3] = the pass is
+// skipped whole, rv = R^{-1} (fp32) and rr = R as pip_fused_kernel's rsave gets it (the
+// identity for a skipped pass); the caller's barrier publishes them.
+__device__ __forceinline__ void pair_side(const double* gd, int c, float skip_tol, int* skipped,
+                                          int* flags, int* any_flag, int* sticky, double* part,
+                                          int* badw, int* blist, float* rv, double* rr, int tid) {
+  const int nblk = c >> 3;
+  const bool skip_whole = skip_tol < 0.f;
+  skip_tol = fabsf(skip_tol);
+  int* bflag = reinterpret_cast<int*>(part);
+  if (skip_tol > 0.f) {
+    const int lane = tid & 63;
+    const double thr = (double)skip_tol * (double)skip_tol *
+                       fmax(gd[(c + (lane & 7)) * 8 + (lane & 7)], 1e-300);
+    for (int bk = tid >> 6; bk < nblk; bk += 4) {
+      const double g = gd[bk * 64 + lane];
+      const unsigned long long bm = __ballot(g * g > thr);
+      if (lane == 0) bflag[bk] = bm != 0ull;
+    }
+    __syncthreads();
+  }
+  int zz_off = 0;
+  if (skip_tol > 0.f && tid < 64) {
+    const int i = tid >> 3, j = tid & 7;
+    zz_off = __ballot(fabs(gd[(c + i) * 8 + j] - (i == j ? 1.0 : 0.0)) > (double)skip_tol) != 0ull;
+  }
+  if (tid < 64) {
+    bool any_on = false;
+    for (int c0 = 0; c0 < nblk; c0 += 64) {
+      const int bk = c0 + tid;
+      const bool on = bk < nblk && (skip_tol <= 0.f || bflag[bk] != 0);
+      any_on |= __ballot(on) != 0ull;
+    }
+    const bool all = skip_whole && any_on;
+    int count = 0;
+    for (int c0 = 0; c0 < nblk; c0 += 64) {
+      const int bk = c0 + tid;
+      const bool on = bk < nblk && (all || skip_tol <= 0.f || bflag[bk] != 0);
+      const unsigned long long m = __ballot(on);
+      if (on) blist[count + __popcll(m & ((1ull << tid) - 1ull))] = bk;
+      if (skipped && on && skip_tol > 0.f) atomicAdd(skipped + 1 + bk, 1);  // histogram
+      count += __popcll(m);
+    }
+    if (tid == 0) {
+      badw[0] = 0;
+      badw[1] = count;
+      badw[2] = zz_off;
+      badw[3] = 0;
+    }
+  }
+  __syncthreads();
+  const int napply = badw[1];
+  if (skip_tol > 0.f && napply == 0 && !badw[2]) {  // (uniform: every thread reads the same words)
+    if (tid < 8) flags[tid] = 0;
+    if (tid < 64) rr[tid] = (tid >> 3) == (tid & 7) ? 1.0 : 0.0;
+    if (tid == 0) {
+      *any_flag = 0;
+      if (skipped) atomicAdd(skipped, 1);
+    }
+    if (tid == 0) badw[3] = 1;
+    return;
+  }
+  {
+    const int e = tid & 63, sl = tid >> 6, i = e >> 3, j = e & 7;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int q = sl; q < napply; q += 4) {
+      const double* g = gd + blist[q] * 64;
+#pragma unroll
+      for (int r = 0; r < 8; r += 4) {
+        a0 += g[r * 8 + i] * g[r * 8 + j];
+        a1 += g[(r + 1) * 8 + i] * g[(r + 1) * 8 + j];
+        a2 += g[(r + 2) * 8 + i] * g[(r + 2) * 8 + j];
+        a3 += g[(r + 3) * 8 + i] * g[(r + 3) * 8 + j];
+      }
+    }
+    part[sl * 64 + e] = (a0 + a1) + (a2 + a3);
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const int i = tid >> 3, j = tid & 7;
+    const double v = 0.5 * (gd[(c + i) * 8 + j] + gd[(c + j) * 8 + i]);
+    part[tid] = v - part[tid] - part[64 + tid] - part[128 + tid] - part[192 + tid];
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const int i = tid >> 3, j = tid & 7;
+    double R[8][8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+      for (int q = r; q < 8; ++q) R[r][q] = part[r * 8 + q];
+    double zmax = 0.0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) zmax = fmax(zmax, gd[(c + r) * 8 + r]);
+    const double zfloor = 1e-30 * zmax;
+    int bad = 0, cancel = 0;
+    double rinv[8];
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+      const double p = R[jj][jj];
+      const double zz = gd[(c + jj) * 8 + jj];
+      const bool cn = !(p > PIP_CANCEL * zz);
+      const bool bj = !(zz > zfloor) || !(p == p) || cn;  // (a later pass: cancelled -> refilled)
+      const bool cj = !bj && cn;
+      bad |= (int)bj << jj;
+      cancel |= (int)cj << jj;
+      const double pe = bj ? 1.0 : (cj ? PIP_CANCEL * zz : p);
+      const double r = rsq_nr(pe);
+#pragma unroll
+      for (int q = jj + 1; q < 8; ++q) R[jj][q] = (bj || cj) ? 0.0 : R[jj][q] * r;
+      R[jj][jj] = bj ? 1.0 : pe * r;
+      rinv[jj] = bj ? 1.0 : r;
+#pragma unroll
+      for (int a = jj + 1; a < 8; ++a)
+#pragma unroll
+        for (int q = a; q < 8; ++q) R[a][q] -= R[jj][a] * R[jj][q];
+    }
+    {
+      double rij = 0.0;
+#pragma unroll
+      for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int q = r; q < 8; ++q) rij = (i == r && j == q) ? R[r][q] : rij;
+      rr[tid] = ((bad >> i) & 1) ? 0.0 : rij;
+    }
+    double xv[8];
+#pragma unroll
+    for (int a = 7; a >= 0; --a) {
+      double t = (a == j) ? 1.0 : 0.0;
+#pragma unroll
+      for (int k = a + 1; k < 8; ++k) t -= R[a][k] * xv[k];
+      xv[a] = t * rinv[a];
+    }
+    double x = xv[0];
+#pragma unroll
+    for (int a = 1; a < 8; ++a) x = (i == a) ? xv[a] : x;
+    rv[tid] = ((bad >> j) & 1) ? 0.f : (float)x;
+    if (tid == 0) badw[0] = bad;
+    if (tid < 8) flags[tid] = (bad >> tid) & 1;
+    if (tid == 0) {
+      *any_flag = (bad | cancel) != 0;
+      if ((bad | cancel) && sticky) *sticky = 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void pair_plan_kernel(double* __restrict__ g2, int nblk_all,
+                                                        int nq_old, float skip_tol, int* skipped,
+                                                        int* flags, int* any_flag, int* sticky,
+                                                        int* __restrict__ plan, int umax) {
+  // LDS: Za's Gram ((c + 8) x 8) | Zb's ((c + 16) x 8) | part 4 x 64, all fp64
+  extern __shared__ __attribute__((aligned(16))) double pp_lds[];
+  __shared__ double dr[64], rra[64], rrb[64];
+  __shared__ float rva[64], rvb[64];
+  __shared__ int bwa[4], bwb[4], nun;
+  __shared__ int bla[N2V2R_BAND_MAXC / 8 + 1], blb[N2V2R_BAND_MAXC / 8 + 1];
+  __shared__ int umask[N2V2R_BAND_MAXC / 8], ulist[N2V2R_BAND_MAXC / 8];
+  const int tid = threadIdx.x;
+  const int c = nq_old * 8;
+  double* gda = pp_lds;
+  double* gdb = gda + (c + 8) * 8;
+  double* part = gdb + (c + 16) * 8;
+  double* gb = g2 + (int64_t)nblk_all * 64;
+  stage_to_lds<256, 16>(gda, g2, (c + 8) * 8, tid);
+  stage_to_lds<256, 16>(gdb, gb, (c + 16) * 8, tid);
+  __syncthreads();
+  pair_side(gda, c, skip_tol, skipped, flags, any_flag, sticky, part, bwa, bla, rva, rra, tid);
+  __syncthreads();
+  // Zb's Gram against the corrected Za' (pair_fixup_kernel): over all of Q's rows of both Grams
+  {
+    const int q = tid >> 6, e = tid & 63, i = e >> 3, j = e & 7;
+    double s = 0.0;
+    for (int r = q; r < c; r += 4) s += gda[r * 8 + i] * gdb[r * 8 + j];
+    part[q * 64 + e] = s;
+  }
+  __syncthreads();
+  if (tid < 64)
+    dr[tid] = gdb[c * 8 + tid] - ((part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]));
+  __syncthreads();
+  if (tid < 8) {
+    double d[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      double v = dr[k * 8 + tid];
+#pragma unroll
+      for (int m = 0; m < k; ++m) v -= rra[m * 8 + k] * d[m];
+      d[k] = v / rra[k * 8 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      gdb[c * 8 + k * 8 + tid] = d[k];
+      gb[(int64_t)nq_old * 64 + k * 8 + tid] = d[k];  // (as the fixup launch leaves the Gram)
+    }
+  }
+  __syncthreads();
+  pair_side(gdb, c + 8, skip_tol, skipped, flags, any_flag, sticky, part, bwb, blb, rvb, rrb, tid);
+  for (int e = tid; e < nq_old; e += 256) umask[e] = 0;
+  __syncthreads();
+  const int na = bwa[1], nb = bwb[1];  // (a skipped pass has an empty list)
+  for (int e = tid; e < na; e += 256) umask[bla[e]] = 1;
+  __syncthreads();
+  for (int e = tid; e < nb; e += 256)
+    if (blb[e] < nq_old) umask[blb[e]] |= 2;
+  __syncthreads();
+  if (tid < 64) {
+    int count = 0;
+    for (int c0 = 0; c0 < nq_old; c0 += 64) {
+      const int bk = c0 + tid;
+      const int mk = bk < nq_old ? umask[bk] : 0;
+      const unsigned long long m = __ballot(mk != 0);
+      if (mk) ulist[count + __popcll(m & ((1ull << tid) - 1ull))] = bk | (mk << 16);
+      count += __popcll(m);
+    }
+    if (tid == 0) nun = count;
+  }
+  __syncthreads();
+  const int nu = nun;
+  if (tid == 0) {
+    const bool za = nb > 0 && blb[nb - 1] == nq_old;  // (ascending: Za' can only come last)
+    plan[0] = nu;
+    plan[1] = (bwa[3] ? 1 : 0) | (bwb[3] ? 2 : 0) | (za ? 4 : 0);
+    plan[2] = bwa[3] ? 0 : bwa[0];
+    plan[3] = bwb[3] ? 0 : bwb[0];
+  }
+  if (tid >= 4 && tid < PAIR_PLAN_HDR) plan[tid] = 0;
+  float* pf = reinterpret_cast<float*>(plan);
+  if (tid < 64) {
+    pf[PAIR_PLAN_HDR + tid] = bwa[3] ? 0.f : rva[tid];
+    pf[PAIR_PLAN_HDR + 64 + tid] = bwb[3] ? 0.f : rvb[tid];
+    pf[PAIR_PLAN_HDR + 128 + tid] = (float)gdb[c * 8 + tid];
+  }
+  for (int e = tid; e < umax; e += 256) plan[PAIR_PLAN_LIST + e] = e < nu ? ulist[e] : 0;
+  float* coef = pf + PAIR_PLAN_LIST + umax;
+  for (int e = tid; e < nu * 128; e += 256) {
+    const int u = ulist[e >> 7], bk = u & 0xFFFF, side = (e >> 6) & 1, w = e & 63;
+    float v = 0.f;
+    if ((u >> 16) & (1 << side)) v = (float)(side ? gdb : gda)[bk * 64 + w];
+    coef[e] = v;
+  }
+}
+
+template <int QB, int NU, bool NT>
+__global__ __launch_bounds__(256) void pip_pair_kernel(BlockList Q, float* Za, float* Zb,
+                                                       const int* __restrict__ plan, int umax,
+                                                       int64_t n, uint64_t seed_a,
+                                                       uint64_t seed_b, int64_t row0) {
+  const int tid = threadIdx.x;
+  extern __shared__ __attribute__((aligned(16))) int pl[];
+  const int nun = plan[0];
+  {
+    // the plan's words in use, all of a thread's loads in flight before its first LDS write
+    const int n4 = (PAIR_PLAN_LIST + umax + nun * 128) / 4;  // (umax: a multiple of 4)
+    for (int e0 = tid; e0 < n4; e0 += 256 * 8) {
+      int4 t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[u] = reinterpret_cast<const int4*>(plan)[min(e0 + 256 * u, n4 - 1)];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) reinterpret_cast<int4*>(pl)[min(e0 + 256 * u, n4 - 1)] = t[u];
+    }
+  }
+  __syncthreads();
+  const int pflags = pl[1];
+  const bool skip_a = pflags & 1, skip_b = pflags & 2, b_za = pflags & 4;
+  if (skip_a && skip_b) return;
+  const int bad_a = pl[2], bad_b = pl[3];
+  const float* rva = reinterpret_cast<const float*>(pl) + PAIR_PLAN_HDR;
+  const float* rvb = rva + 64;
+  const float* cza = rva + 128;
+  const int* ulist = pl + PAIR_PLAN_LIST;
+  const float* coef = reinterpret_cast<const float*>(pl) + PAIR_PLAN_LIST + umax;
+  // rows and lanes as pip_fused_kernel
+  const int lane = tid & 63, h = lane & 1, ro = lane >> 1;
+  const int64_t rbase = (int64_t)blockIdx.x * (128 * NU) + (tid >> 6) * (32 * NU) + ro;
+  if (rbase >= n) return;
+  int64_t rw[NU];
+  bool okr[NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    okr[u] = rbase + 32 * u < n;
+    rw[u] = okr[u] ? rbase + 32 * u : rbase;
+  }
+  float aa[NU][8], ab[NU][8];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    f32x4 z = {0.f, 0.f, 0.f, 0.f}, y = {0.f, 0.f, 0.f, 0.f};
+    if (!skip_a) z = *reinterpret_cast<const f32x4*>(Za + rw[u] * 8 + 4 * h);
+    if (!skip_b) y = *reinterpret_cast<const f32x4*>(Zb + rw[u] * 8 + 4 * h);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      aa[u][t] = h ? 0.f : z[t];
+      aa[u][4 + t] = h ? z[t] : 0.f;
+      ab[u][t] = h ? 0.f : y[t];
+      ab[u][4 + t] = h ? y[t] : 0.f;
+    }
+  }
+  auto apply = [&](float (&acc)[NU][8], const f32x4 (&a4)[NU], const float* g) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float gv = g[m * 8 + j];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) acc[u][j] -= a4[u][m] * gv;
+      }
+  };
+  auto load = [&](f32x4 (&a4)[NU], int bk) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      a4[u] = NT ? __builtin_nontemporal_load(
+                       reinterpret_cast<const f32x4*>(Q.blk[bk] + rw[u] * 8 + 4 * h))
+                 : *reinterpret_cast<const f32x4*>(Q.blk[bk] + rw[u] * 8 + 4 * h);
+  };
+  int q = 0;
+  for (; q + QB <= nun; q += QB) {  // QB blocks x NU rows in flight
+    f32x4 a4[QB][NU];
+    int ue[QB];
+#pragma unroll
+    for (int b4 = 0; b4 < QB; ++b4) ue[b4] = __builtin_amdgcn_readfirstlane(ulist[q + b4]);
+#pragma unroll
+    for (int b4 = 0; b4 < QB; ++b4) load(a4[b4], ue[b4] & 0xFFFF);
+#pragma unroll
+    for (int b4 = 0; b4 < QB; ++b4) {
+      const float* g = coef + (q + b4) * 128 + 4 * h * 8;
+      if (ue[b4] & (1 << 16)) apply(aa, a4[b4], g);
+      if (ue[b4] & (2 << 16)) apply(ab, a4[b4], g + 64);
+    }
+  }
+  for (; q < nun; ++q) {
+    f32x4 a4[NU];
+    const int ue = __builtin_amdgcn_readfirstlane(ulist[q]);
+    load(a4, ue & 0xFFFF);
+    const float* g = coef + q * 128 + 4 * h * 8;
+    if (ue & (1 << 16)) apply(aa, a4, g);
+    if (ue & (2 << 16)) apply(ab, a4, g + 64);
+  }
+  // Z' = (.) R^{-1}, flagged columns refilled: pip_fused_kernel's epilogue
+  auto finish = [&](float (&acc)[8], const float* rv, int bad, uint64_t seed, int64_t row) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      acc[j] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[j]), 0xB1, 0xF, 0xF, false));
+    float o[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int jo = 4 * h + t;
+      float sum = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum += (j <= jo) ? acc[j] * rv[j * 8 + jo] : 0.f;
+      o[t] = ((bad >> jo) & 1) ? counter_normal(seed, (uint64_t)(row0 + row) * 64 + jo) : sum;
+    }
+    return f32x4{o[0], o[1], o[2], o[3]};
+  };
+  f32x4 oa[NU];  // this lane's column half of Za' (of Za as it is when its pass is skipped)
+  if (!skip_a) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      oa[u] = finish(aa[u], rva, bad_a, seed_a, rw[u]);
+      if (okr[u]) *reinterpret_cast<f32x4*>(Za + rw[u] * 8 + 4 * h) = oa[u];
+    }
+  } else if (b_za) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) oa[u] = *reinterpret_cast<const f32x4*>(Za + rw[u] * 8 + 4 * h);
+  }
+  if (skip_b) return;
+  if (b_za) apply(ab, oa, cza + 4 * h * 8);
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const f32x4 o = finish(ab[u], rvb, bad_b, seed_b, rw[u]);
+    if (okr[u]) *reinterpret_cast<f32x4*>(Zb + rw[u] * 8 + 4 * h) = o;
+  }
+}
+
+// g2: the pair's two Grams [2][nq_old + 2][64] (ts_tn2; Zb's rows against Za are rewritten as
+// pair_fixup leaves them).  plan: PAIR_PLAN_LIST + (nq_old rounded up to 4) * 129 words.
+// hipErrorNotSupported: the plan does not fit (the caller runs the three-launch path).
+extern "C" hipError_t n2v2r_launch_pip_pair(const BlockList& Q, float* Za, float* Zb, double* g2,
+                                            int64_t n, int* flags, int* any_flag, int* sticky,
+                                            uint64_t seed_a, uint64_t seed_b, int64_t row0,
+                                            float skip_tol, int* skipped, int* plan,
+                                            size_t plan_bytes, hipStream_t stream) {
+  const int nq_old = Q.count, c = nq_old * 8;
+  if (Q.width != 8 || nq_old < 0) return hipErrorInvalidValue;
+  const int umax = (nq_old + 3) & ~3;
+  if (c + 8 > N2V2R_BAND_MAXC || plan_bytes < sizeof(int) * (PAIR_PLAN_LIST + (size_t)umax * 129))
+    return hipErrorNotSupported;
+  const size_t lds_plan = sizeof(double) * ((size_t)(2 * c + 24) * 8 + 256);
+  const size_t lds = sizeof(int) * (PAIR_PLAN_LIST + (size_t)umax * 129);
+  static const hipError_t attr = [] {
+    hipError_t e = hipFuncSetAttribute((const void*)pair_plan_kernel,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024);
+    (void)hipGetLastError();
+    return e;
+  }();
+  if (attr != hipSuccess || lds_plan > 112 * 1024 || lds > 64 * 1024) return hipErrorNotSupported;
+  hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(256), lds_plan, stream, g2, nq_old + 2, nq_old,
+                     skip_tol, skipped, flags, any_flag, sticky, plan, umax);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int rows = n >= (int64_t)1 << 19 ? 512 : 256;  // as pip_fused (256 at cfg4: the same fit time)
+  const unsigned grid = (unsigned)((n + rows - 1) / rows);
+#define PAIR_LAUNCH(QB_, NU_, NT_)                                                               \
+  hipLaunchKernelGGL((pip_pair_kernel<QB_, NU_, NT_>), dim3(grid ? grid : 1), dim3(256), lds,    \
+                     stream, Q, Za, Zb, plan, umax, n, seed_a, seed_b, row0)
+  const bool nt = basis_nt(n, Q.count + 1);
+  if (rows == 256) {
+    if (nt) PAIR_LAUNCH(4, 2, true); else PAIR_LAUNCH(4, 2, false);
+  } else {
+    if (nt) PAIR_LAUNCH(2, 4, true); else PAIR_LAUNCH(2, 4, false);
+  }
+#undef PAIR_LAUNCH
+  return hipGetLastError();
+}
+
 // Fill an N x W block with N(0,1) deviates: all columns (flags == nullptr) or only flagged ones.
 __global__ void fill_normal_kernel(float* __restrict__ blk, int w, int64_t n, uint64_t seed,
                                    const int* flags, const int* cond, uint64_t ctr0) {

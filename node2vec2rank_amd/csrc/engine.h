@@ -90,6 +90,12 @@ hipError_t n2v2r_launch_ts_tn2(const BlockList& A, const float* Za, const float*
 hipError_t n2v2r_launch_rmul8(const double* r2, double* r1, hipStream_t stream);
 hipError_t n2v2r_launch_pair_fixup(double* g2, int nblk_all, int nq_old, double* ra,
                                    hipStream_t stream);
+// words of the paired apply's plan for the largest basis (dense.hip, pair_plan_kernel)
+constexpr size_t N2V2R_PAIR_PLAN_WORDS = 208 + (size_t)(N2V2R_BAND_MAXC / 8) * 129;
+hipError_t n2v2r_launch_pip_pair(const BlockList& Q, float* Za, float* Zb, double* g2, int64_t n,
+                                 int* flags, int* any_flag, int* sticky, uint64_t seed_a,
+                                 uint64_t seed_b, int64_t row0, float skip_tol, int* skipped,
+                                 int* plan, size_t plan_bytes, hipStream_t stream);
 hipError_t n2v2r_launch_pip_fused(const BlockList& Q, const float* Zin, float* Zout,
                                   const double* G, int c, int64_t n, const int* cond, int* flags,
                                   int* any_flag, double* save, int save_row0, int save_rows,
@@ -468,6 +474,7 @@ struct EigWorkspace {
   DevBuf tflag;                               // partitioned: a per-cycle flag agreed over ranks
   DevBuf s2part;                             // [K][npad][8] XCD-split second-stage outputs
   DevBuf g2, pair_ra;                         // paired full passes: the two Grams, R of the first
+  DevBuf pair_plan;                           // ... and the paired apply's plan
   DevBuf sturm;                               // Sturm Rayleigh-Ritz: assembled arrow + band
   DevBuf rres;                                // lean images: R of the restart projection
   DevBuf skipc;                               // full passes skipped (selective reorthogonalisation)

@@ -145,6 +145,7 @@ struct Eig {
   // image keeps the uncorrected block, whose components along older blocks are removed from
   // the next block by that block's full pass.  `deferred`: the block awaiting its full pass.
   bool defer = false, pair_gram = true;
+  bool pair_apply = false;  // a pair's two selective passes in one launch (N2V2R_PAIR_APPLY)
   float* deferred = nullptr;
   struct LeanRetry {};
   // Gram scratch of the orthogonalisation passes (the workspace's)
@@ -719,8 +720,10 @@ struct Eig {
   // The full passes of the deferred block Za (the last block of `basis`) and of the new block
   // Zb in one read of the old basis Q: G = [Q Za Zb]^T [Za Zb] (ts_tn_stream2), Za's selective
   // pass against Q (its R kept), Zb's Gram against the corrected Za (pair_fixup), Zb's selective
-  // pass against [Q Za].  false when the two-block Gram does not apply (then the caller runs the
-  // two passes one after the other).
+  // pass against [Q Za] -- planned by one small launch and applied by one that loads each basis
+  // block once for both (pip_pair, N2V2R_PAIR_APPLY=fused), or as three launches (the default).
+  // false when the two-block Gram does not apply (then the caller runs the two passes one after
+  // the other).
   bool pair_pass(float* zb, const std::vector<float*>& basis) {
     if (!deferred || basis.empty() || basis.back() != deferred) return false;
     const int nq_old = (int)basis.size() - 1;
@@ -740,6 +743,21 @@ struct Eig {
     if (h->comm) h->allreduce_f64(g2, 2 * (size_t)(nq_old + 2) * 64);
     double* ra = h->ews.pair_ra.as<double>();
     int* skc = reorth_tol != 0.f ? h->ews.skipc.as<int>() : nullptr;
+    if (pair_apply) {
+      // both selective passes in one read of the basis (the seeds the two launches below take)
+      const uint64_t sa = seed ^ (0xABCDull + (fill_counter + 1));
+      const uint64_t sb = seed ^ (0xABCDull + (fill_counter + 2));
+      const hipError_t pe = n2v2r_launch_pip_pair(
+          blocks(basis, 0, nq_old), deferred, zb, g2, n, flg_p + 64, any_p + 1, any_p + 3, sa, sb,
+          row0, reorth_tol, skc, h->ews.pair_plan.as<int>(), h->ews.pair_plan.bytes, st);
+      if (pe == hipSuccess) {
+        fill_counter += 2;
+        t_ortho += now_ms() - t0;
+        deferred = nullptr;
+        return true;
+      }
+      if (pe != hipErrorNotSupported) throw HipFail{pe, "n2v2r_launch_pip_pair"};
+    }
     HIPCHK(n2v2r_launch_pip_fused(blocks(basis, 0, nq_old), deferred, deferred, g2, nq_old * b, n,
                                   nullptr, flg_p + 64, any_p + 1, nullptr, 0, 0, any_p + 3,
                                   seed ^ (0xABCDull + ++fill_counter), row0, ra, reorth_tol, skc,
@@ -1213,6 +1231,16 @@ struct Eig {
       defer = !(e && e[0] == '0') && b == 8 && pip_fused() && lean;
       deferred = nullptr;
       pair_gram = true;  // (the A/B switch of the pairing retired in round 5)
+      // a pair's two selective passes: fused (planned by one small launch, applied in one read
+      // of the basis) from 2^19 rows on, where the second read of the basis costs more than the
+      // serial plan launch (cfg4 against cfg2); below that split (three launches:
+      // apply, fixup, apply -- also the fused form's reference and its fall-back).
+      // Bit-identical fits.  N2V2R_PAIR_APPLY=fused / split forces one; read per fit (tests,
+      // A/B runs)
+      const char* pa = std::getenv("N2V2R_PAIR_APPLY");
+      pair_apply = pa && std::strcmp(pa, "fused") == 0   ? true
+                   : pa && std::strcmp(pa, "split") == 0 ? false
+                                                         : n >= (int64_t)1 << 19;
       if (defer) {
         h->ews.g2.ensure(sizeof(double) * 2 * (size_t)(nb_max + 2) * 64, st);
         // R of the pair's first pass: the identity until a pass writes it
@@ -1221,6 +1249,7 @@ struct Eig {
                                        0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0,
                                        0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1};
         h->ews.pair_ra.ensure(sizeof(double) * 64, st);
+        h->ews.pair_plan.ensure(sizeof(int) * N2V2R_PAIR_PLAN_WORDS, st);
         HIPCHK(hipMemcpyAsync(h->ews.pair_ra.p, eye, sizeof(eye), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
       }
