@@ -44,13 +44,6 @@ hipError_t n2v2r_launch_row_sums(const CsrDev& A, float* out, hipStream_t stream
 hipError_t n2v2r_launch_spmm_tile(const SpmmTileArgs& a, hipStream_t stream);
 hipError_t n2v2r_launch_chunk_major_keys(uint64_t* keys, int64_t nnz, int64_t npad, int W,
                                          int64_t rc, hipStream_t stream);
-// paired-panel mode (pair.hip)
-hipError_t n2v2r_launch_interleave16(const float* za, const float* zb, float* x16, int64_t n,
-                                     hipStream_t stream);
-hipError_t n2v2r_launch_pair_h_assemble(const double* hcol, int64_t ldcol, const int* lo,
-                                        const int* nr, int s0, int ns, int kp,
-                                        const double* theta, double* H, int c,
-                                        hipStream_t stream);
 int n2v2r_spmm_tile_rows(int64_t n, int ncu, int wpc, int wbits);
 int n2v2r_spmm_tile_rows_b(int64_t n, int ncu, int wpc, int wbits, int b);
 hipError_t n2v2r_launch_cb_count(const CsrDev& A, int64_t cw, int nb, int32_t* cnt,
@@ -479,9 +472,6 @@ struct EigWorkspace {
   DevBuf rres;                                // lean images: R of the restart projection
   DevBuf skipc;                               // full passes skipped (selective reorthogonalisation)
   DevBuf tblk;                                // tiled SpMM: CsrBlk [2][K][nb] (stage 1, stage 2)
-  // paired-panel mode: the N x 16 panel of two blocks, the saved band columns of the projected
-  // matrix (one slot of (c + 8) x 8 per basis block), the restart pair's coupling rows
-  DevBuf x16, hcol, pcab, pth;
 };
 }  // namespace n2v2r_int
 

@@ -730,16 +730,11 @@ __global__ __launch_bounds__(1024, WPC == 1 ? 4 : 8) void spmm16_flat_kernel(Spm
     }
     if (!a.sum || k == a.K - 1) {
       float* Y = a.Y[a.sum ? 0 : k];
-      // split output (paired mode): lane quarter sub < 2 writes Y[0]'s row, sub >= 2 Y2's
-      const bool split = a.sum && a.Y2;
-      float* Yq = split ? (sub < 2 ? Y : a.Y2) : Y;
-      const int64_t ld = split ? 8 : a.ldy;
-      const int co = split ? (sub & 1) * 4 : sub * 4;
       for (int w = wave; w < nwin; w += nwave)
         for (int rr = q; rr < W; rr += 16) {
           const int lr = (w << wbits) + rr;
           if (lr < nrows) {
-            *reinterpret_cast<f32x4*>(Yq + (r0 + lr) * ld + co) = tacc[lr * 4 + sub];
+            *reinterpret_cast<f32x4*>(Y + (r0 + lr) * a.ldy + sub * 4) = tacc[lr * 4 + sub];
             tacc[lr * 4 + sub] = zero;
           }
         }

@@ -65,7 +65,4 @@ struct SpmmTileArgs {  // row tiles x column-block phases (spmm8/16_flat_kernel)
   int tile_rows;       // a multiple of the window rows 2^wbits
   int wbits;           // window rows = 2^wbits (CB_WIN_BITS_MIN..MAX), as the blocks were packed
   int width;           // panel width b: 8 (spmm8_flat_kernel) or 16 (spmm16_flat_kernel); 0 = 8
-  // width 16, sum mode: non-null splits the output -- columns 0-7 to Y[0], 8-15 to Y2, both
-  // N x 8 (ld 8): the two 8-wide basis blocks of the solver's paired mode (pair.hip)
-  float* Y2;
 };
