@@ -69,7 +69,12 @@ enum { N2V2R_EIG_FULL_FIRST_PASS = 1, N2V2R_EIG_DENSE_RR = 2,
        /* bits 256 and 512 are retired (the paired-panel mode's switches): not to be reused */
        N2V2R_EIG_TEST_FAIL_ALONE = 128 /* tests, multi-GPU handles: rank 1 fails alone after its
                                           first block application while its peers go on into
-                                          their next collective (the abort path) */ };
+                                          their next collective (the abort path) */,
+       N2V2R_EIG_TEST_TRI_TIMEOUT = 1024 /* tests: the first time a fit reads the multi-workgroup
+                                            tridiagonalisation's error word it is treated as set
+                                            (the host discards a good result and redoes the step
+                                            with the one-workgroup kernel; nothing on the GPU is
+                                            made to time out) */ };
 
 typedef struct n2v2r_handle n2v2r_handle;
 typedef struct n2v2r_simgroup n2v2r_simgroup;

@@ -20,7 +20,8 @@ int n2v2r_bench_spmm(n2v2r_handle* h, int k, int transpose, int b, int reps, con
                      float* Y, double* avg_ms, double* algo_bytes);
 /* The flat-window tiled SpMM of layer k (A_k X, or A_k^T X) at panel width b = 8 with nb column
  * blocks (0: panel blocks of <= 2 MB, at most 32), one-GPU handles; Y (optional, n x 8) receives
- * the product.  N2V2R_ERR_BAD_ARG when the layer cannot take packed blocks. */
+ * the product.  N2V2R_ERR_BAD_ARG when b != 8 (the b = 16 tiled kernel was retired; the
+ * parameter keeps the signature) or when the layer cannot take packed blocks. */
 int n2v2r_bench_spmm_tiled(n2v2r_handle* h, int k, int transpose, int b, int nb, int reps,
                            const float* X, float* Y, double* avg_ms);
 

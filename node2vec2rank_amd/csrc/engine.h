@@ -45,7 +45,6 @@ hipError_t n2v2r_launch_spmm_tile(const SpmmTileArgs& a, hipStream_t stream);
 hipError_t n2v2r_launch_chunk_major_keys(uint64_t* keys, int64_t nnz, int64_t npad, int W,
                                          int64_t rc, hipStream_t stream);
 int n2v2r_spmm_tile_rows(int64_t n, int ncu, int wpc, int wbits);
-int n2v2r_spmm_tile_rows_b(int64_t n, int ncu, int wpc, int wbits, int b);
 hipError_t n2v2r_launch_cb_count(const CsrDev& A, int64_t cw, int nb, int32_t* cnt,
                                  hipStream_t stream);
 hipError_t n2v2r_launch_cb_rowptrs(const int32_t* cnt, int64_t n, int nb, int64_t nnz,

@@ -30,10 +30,6 @@ struct SpmmArgs {
 #define CB_MAX 128   // column blocks per layer at most (N2V2R_SPMM_TILE_NB)
 #define CB_WIN_BITS_MIN 5  // windows of 2^wbits rows: 32 ..
 #define CB_WIN_BITS_MAX 7  //                          .. 128 (row-in-window bits of a packed entry)
-// b = 16 flat tiles: workgroups per CU (2: 1024-row tiles; 1: 2048-row tiles, spmm16_flat_kernel)
-#ifndef N2V2R_SPMM16_WPC
-#define N2V2R_SPMM16_WPC 2
-#endif
 
 // One column block of a layer, packed for the flat tiled form: entry = (row % W) << cbits |
 // (column - col0), W = 2^wbits rows per window, in the layer's shared index array starting at
@@ -53,7 +49,7 @@ struct CsrBlk {
   int64_t col0;            // first column of the block
 };
 
-struct SpmmTileArgs {  // row tiles x column-block phases (spmm8/16_flat_kernel)
+struct SpmmTileArgs {  // row tiles x column-block phases (spmm8_flat_kernel)
   const CsrBlk* blk;   // device array [K][nb]
   const float* X[SPMM_MAX_LAYERS];  // panel per layer (gathered, global rows)
   float* Y[SPMM_MAX_LAYERS];        // output per layer (sum: Y[0])
@@ -64,5 +60,4 @@ struct SpmmTileArgs {  // row tiles x column-block phases (spmm8/16_flat_kernel)
   int sum;
   int tile_rows;       // a multiple of the window rows 2^wbits
   int wbits;           // window rows = 2^wbits (CB_WIN_BITS_MIN..MAX), as the blocks were packed
-  int width;           // panel width b: 8 (spmm8_flat_kernel) or 16 (spmm16_flat_kernel); 0 = 8
 };

@@ -586,24 +586,6 @@ def test_fit_register_windows_bit_identical(engine, monkeypatch):
     assert np.array_equal(engine.left_embedding(), U0)
 
 
-@pytest.mark.parametrize("wbits", ["5", "7"])
-@pytest.mark.parametrize("nb", [4, 32])
-def test_spmm16_tiled_flat_blocks(engine, monkeypatch, tiled_layer, nb, wbits):
-    """The b = 16 flat-window kernel (a lane quad per entry, 64-B panel rows) on the same layer:
-    every row against scipy, both orientations (its steps hold 16 entries, not 32: a row's
-    partial sums split at other places than the b = 8 kernel's, so the two agree to rounding)."""
-    monkeypatch.setenv("N2V2R_SPMM_WBITS", wbits)
-    A, X, _ = tiled_layer
-    X16 = np.ascontiguousarray(np.concatenate([X, X[::-1] * 0.5], axis=1))
-    engine.set_layers([A])
-    for tr in (False, True):
-        M = (A.T if tr else A).tocsr().astype(np.float64)
-        ref = M @ X16.astype(np.float64)
-        bound = 1e-5 * (abs(M) @ np.abs(X16).astype(np.float64)) + 1e-6
-        Y16, _ = engine.bench_spmm_tiled(0, X16, transpose=tr, nb=nb, reps=2)
-        assert np.all(np.abs(Y16 - ref) <= bound), (nb, wbits, tr)
-
-
 @pytest.mark.parametrize("d", [60, 64, 100, 128])
 def test_embedding_from_lean_check_bit_identical(engine, monkeypatch, d):
     """With the tiled SpMM on one GPU, the final lean check's stage-1 products A_k^T X of the d
@@ -1008,10 +990,20 @@ def test_uase_large_kept_set_sturm_failure_dense_from_band(engine):
     Sturm Rayleigh-Ritz; forced to fail there (test flag 32), each cycle's fallback is the dense
     Rayleigh-Ritz on H expanded from the saved band (rr_band_expand_kernel), not a refit without
     lean images.  Both fits: every pair converged, the same singular values, host fp64
-    residuals."""
+    residuals.  A third fit also discards the first multi-workgroup tridiagonalisation of that
+    dense step (test flag 1024), so the step is retried from the band with the one-workgroup
+    kernel: one tridiagonalisation fallback, the same values and residuals."""
     from node2vec2rank_amd import synthetic
     layers = synthetic.er_layers(60_001, 20, 2, seed_base=77)
     d = 128
+    cols = [0, d // 2, d - 1]
+    A = sp.hstack(layers).tocsr().astype(np.float64)
+
+    def host_residuals(s):
+        X = engine.left_embedding().astype(np.float64)[:, cols]
+        X /= np.sqrt(s[cols])[None, :]
+        return np.linalg.norm(A @ (A.T @ X) - X * (s[cols] ** 2)[None, :], axis=0) / s[0] ** 2
+
     engine.set_layers(layers)
     st0 = engine.uase(d, seed=5, keep=224)
     s0 = engine.singular_values()
@@ -1021,11 +1013,34 @@ def test_uase_large_kept_set_sturm_failure_dense_from_band(engine):
     assert st["converged"] == d and st["rr_fallbacks"] == st["restarts"], st
     assert st["lean_checks"] > 0 and st0["lean_checks"] > 0, (st0, st)
     np.testing.assert_allclose(s[:d], s0[:d], rtol=1e-5)
-    X = engine.left_embedding().astype(np.float64)[:, [0, d // 2, d - 1]]
-    X /= np.sqrt(s[[0, d // 2, d - 1]])[None, :]
-    A = sp.hstack(layers).tocsr().astype(np.float64)
-    res = np.linalg.norm(A @ (A.T @ X) - X * (s[[0, d // 2, d - 1]] ** 2)[None, :], axis=0) / s[0] ** 2
+    res = host_residuals(s)
     assert res.max() < 1e-5, res
+    st2 = engine.uase(d, seed=5, keep=224, solver_flags=32 | 1024)
+    s2 = engine.singular_values()
+    assert st2["converged"] == d and st2["tri_fallbacks"] == 1, st2
+    assert st2["rr_fallbacks"] == st2["restarts"], st2
+    np.testing.assert_allclose(s2[:d], s0[:d], rtol=1e-5)
+    res2 = host_residuals(s2)
+    assert res2.max() < 1e-5, res2
+
+
+def test_uase_dense_rr_tridiag_timeout_retry_bit_identical(engine, monkeypatch):
+    """Dense Rayleigh-Ritz (flag 2) whose first multi-workgroup tridiagonalisation is discarded
+    (test flag 1024): the step is redone with the one-workgroup kernel, which every later cycle
+    keeps.  The retry recomputes H from Q and W with fixed-order reductions, so the fit issues
+    the launches of a fit that ran the one-workgroup kernel from the start (N2V2R_RR_TRI=1) on
+    the same inputs: bit-identical singular values and left embedding."""
+    from node2vec2rank_amd import synthetic
+    d = 32
+    engine.set_layers(synthetic.er_layers(20_003, 16, 2))
+    st = engine.uase(d, solver_flags=2 | 1024)
+    s, U = engine.singular_values(), engine.left_embedding()
+    assert st["converged"] == d and st["tri_fallbacks"] == 1, st
+    monkeypatch.setenv("N2V2R_RR_TRI", "1")
+    st1 = engine.uase(d, solver_flags=2)
+    assert st1["converged"] == d and st1["tri_fallbacks"] == 0, st1
+    assert np.array_equal(engine.singular_values(), s)
+    assert np.array_equal(engine.left_embedding(), U)
 
 
 @pytest.mark.parametrize("keep,flags", [(168, 0), (168, 32), (256, 0)])
