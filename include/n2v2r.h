@@ -214,6 +214,36 @@ enum { N2V2R_CORR_UNSIGNED = 0, N2V2R_CORR_SIGNED = 1, N2V2R_CORR_SIGNED_HYBRID 
        N2V2R_CORR_RAW = 3 };
 int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples,
                          const double* E /* n x samples, row-major */, int kind, double power);
+/* network_transform (preprocessing_utils.py:116-141) of a loaded DENSE-storage layer, in place in
+ * HBM, whichever call loaded it (n2v2r_set_layer_corr or n2v2r_set_layer_dense): the layer never
+ * visits the host.  With a = the stored fp32 values (as fp64, which is exact):
+ *   1. N2V2R_TF_ABSOLUTE: a <- |a|;
+ *   2. an entry is alive when a != 0 (-0 is zero) and, with N2V2R_TF_THRESHOLD, !(a < threshold);
+ *   3. m = the alive entries of the whole n x n layer (diagonal, both triangles, every rank's rows);
+ *   4. the cut is np.percentile(alive values, q = 100 - top_percent_keep), numpy's arithmetic:
+ *      pos = (m - 1) (q / 100.0), lo = floor(pos), g = pos - lo, hi = min(lo + 1, m - 1), x and y
+ *      the lo-th and hi-th smallest alive values, d = y - x, cut = x + d g when g < 0.5, else
+ *      y - d (1 - g), all fp64 on the host; alive entries with a < cut die (a NaN cut, which only
+ *      infinite values can give, kills nothing, as the reference's comparison);
+ *   5. survivors keep a, or become 1.0f with N2V2R_TF_BINARIZE; every other entry becomes +0.0f.
+ * x and y come from an MSD radix select on the GPU over order-preserving u32 keys of the fp32
+ * bits (four 8-bit passes, then one min pass when y > x): the result equals ingest.transform's on
+ * the same stored values bit for bit.  A directed layer's A^T copy gets the same cut and rule and
+ * stays the exact transpose.  On a partitioned handle the call is collective: the integer digit
+ * histograms, m and the NaN count are summed over the ranks as u64 (exact; no 2^53 guard is
+ * needed), the min is combined, and every rank reaches the same cut, stats and status.
+ * stats (optional): nonzero = m, kept = the survivors, cut = the value of step 4.
+ * The call clears the embedding (n2v2r_uase has to run again).
+ * N2V2R_ERR_BAD_ARG, layer untouched (nothing is written before the cut is known, so the call
+ * can be repeated): a layer that is not loaded; a CSR-storage layer (transform it on the host
+ * with node2vec2rank_amd.ingest.transform before loading it); top_percent_keep outside [0, 100]
+ * or not finite; a NaN threshold with N2V2R_TF_THRESHOLD; unknown flag bits; a NaN in the layer;
+ * m == 0 (the layer has no non-zero entry left; the reference raises IndexError from an empty
+ * percentile there). */
+enum { N2V2R_TF_ABSOLUTE = 1, N2V2R_TF_BINARIZE = 2, N2V2R_TF_THRESHOLD = 4 };
+typedef struct { int64_t nonzero; int64_t kept; double cut; } n2v2r_transform_stats;
+int n2v2r_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
+                          double top_percent_keep, n2v2r_transform_stats* stats /* may be NULL */);
 /* distributed ingest without the global CSR on every rank: the caller's own rows
  * [row0, row0 + n_rows) (must equal n2v2r_dist_info's) of a SYMMETRIC layer, indptr local
  * (starting at 0), column indices global. */

@@ -60,6 +60,17 @@ int n2v2r_h2d_layer_bytes(const n2v2r_handle* h, int64_t* per_rank, int cap);
  * N2V2R_ERR_BAD_ARG when layer k is not a loaded dense layer. */
 int n2v2r_get_layer_dense(n2v2r_handle* h, int k, float* A /* n x n */);
 
+/* One kernel of n2v2r_transform_layer alone on the loaded dense layer k of a one-GPU handle, timed
+ * with one HIP event pair on the engine stream around `reps` launches back to back, after one
+ * warm-up (the roofline of tools/layer_transform_probe.py).  which: 0..3 the radix-select
+ * histogram pass of that index (its prefix = the digits of the layer's median alive key, so every
+ * pass counts a real bucket), 4 the min pass above that key, 5 the apply pass with a cut of -inf
+ * and no flag, which rewrites every entry with its own value (a -0 becomes +0, a NaN 0).
+ * flags / threshold as n2v2r_transform_layer (BINARIZE ignored).  avg_ms = the span / reps;
+ * bytes = the layer bytes one launch reads (the apply pass writes as many again). */
+int n2v2r_bench_transform_pass(n2v2r_handle* h, int k, int which, int flags, double threshold,
+                               int reps, double* avg_ms, double* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,8 @@ EXPORTED = [
     "n2v2r_simgroup_destroy", "n2v2r_create_sim", "n2v2r_dist_info", "n2v2r_set_layer_csr_rows",
     "n2v2r_rr_top", "n2v2r_rr_band_top", "n2v2r_set_layer_dense", "n2v2r_project",
     "n2v2r_create_multi", "n2v2r_multi_devices", "n2v2r_h2d_layer_bytes",
-    "n2v2r_set_layer_corr", "n2v2r_get_layer_dense",
+    "n2v2r_set_layer_corr", "n2v2r_get_layer_dense", "n2v2r_transform_layer",
+    "n2v2r_bench_transform_pass",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -88,6 +89,13 @@ class EigStats(ctypes.Structure):
             out[k] = list(v) if isinstance(v, ctypes.Array) else v
         return out
 
+
+class TransformStats(ctypes.Structure):
+    _fields_ = [("nonzero", ctypes.c_int64), ("kept", ctypes.c_int64), ("cut", ctypes.c_double)]
+
+
+# n2v2r_transform_layer flags (include/n2v2r.h)
+TF_ABSOLUTE, TF_BINARIZE, TF_THRESHOLD = 1, 2, 4
 
 _lib = None
 _lock = threading.RLock()  # re-entered: acquire_engine -> Engine() -> load()
@@ -168,6 +176,11 @@ def load(path: str | None = None):
             "n2v2r_set_layer_corr": (_i, [_vp, _i, _i64, _i64, _p(np.float64), _i,
                                           ctypes.c_double]),
             "n2v2r_get_layer_dense": (_i, [_vp, _i, _p(np.float32)]),
+            "n2v2r_transform_layer": (_i, [_vp, _i, _i, ctypes.c_double, ctypes.c_double,
+                                           ctypes.POINTER(TransformStats)]),
+            "n2v2r_bench_transform_pass": (_i, [_vp, _i, _i, _i, ctypes.c_double, _i,
+                                                ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_double)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -373,6 +386,10 @@ class Engine:
                 else:
                     st = self.lib.n2v2r_set_layer_dense(self.h, k, n, a, int(symmetric))
                 self._check(st, f"layer {k}")
+                if isinstance(a, Coexpression) and a.transforms:
+                    self.transform_layer(k, threshold=a.threshold,
+                                         top_percent_keep=a.top_percent_keep,
+                                         binarize=a.binarize)
             self.n = n
             self.num_layers = len(arrs)
             self.storage = "dense"
@@ -566,6 +583,38 @@ class Engine:
         A = np.zeros((self.n, self.n), dtype=np.float32)
         self._check(self.lib.n2v2r_get_layer_dense(self.h, int(k), A), "layer_dense")
         return A
+
+    def transform_layer(self, k: int, threshold=None, top_percent_keep=100, binarize=False,
+                        absolute=False) -> dict:
+        """``network_transform`` of the loaded dense-storage layer k, in place on the GPU
+        (n2v2r_transform_layer): what ``ingest.transform`` gives on the layer's stored values, bit
+        for bit.  Returns ``{"nonzero", "kept", "cut"}``: the entries alive before the
+        percentile cut, the survivors and the cut.  ``ValueError`` (layer untouched): an
+        argument out of range, a CSR-storage layer, a NaN in the layer, or a layer with no
+        non-zero entry left."""
+        try:
+            thr = 0.0 if threshold is None else float(threshold)
+            top = float(top_percent_keep)
+        except (TypeError, ValueError):
+            raise ValueError("threshold and top_percent_keep must be numbers, got "
+                             f"{threshold!r} and {top_percent_keep!r}") from None
+        flags = ((TF_ABSOLUTE if absolute else 0) | (TF_BINARIZE if binarize else 0) |
+                 (0 if threshold is None else TF_THRESHOLD))
+        st = TransformStats()
+        self._check(self.lib.n2v2r_transform_layer(self.h, int(k), flags, thr, top,
+                                                   ctypes.byref(st)), f"transform_layer {k}")
+        return {"nonzero": int(st.nonzero), "kept": int(st.kept), "cut": float(st.cut)}
+
+    def bench_transform_pass(self, k: int, which: int, threshold=None, absolute=False,
+                             reps: int = 20):
+        """Time one kernel of ``transform_layer`` alone (n2v2r_bench_transform_pass): ``which``
+        0..3 a histogram pass, 4 the min pass, 5 the apply pass.  Returns (ms, bytes read)."""
+        flags = (TF_ABSOLUTE if absolute else 0) | (0 if threshold is None else TF_THRESHOLD)
+        ms, by = ctypes.c_double(), ctypes.c_double()
+        self._check(self.lib.n2v2r_bench_transform_pass(
+            self.h, int(k), int(which), flags, 0.0 if threshold is None else float(threshold),
+            int(reps), ctypes.byref(ms), ctypes.byref(by)), "bench_transform_pass")
+        return ms.value, by.value
 
     def bench_spmm(self, k: int, X, transpose: bool = False, reps: int = 20, want_y=True):
         """Time the SpMM kernel alone (HIP events on the engine stream)."""

@@ -22,12 +22,19 @@ class Coexpression:
     kind: ``"unsigned"`` |r|, ``"signed"`` (1 + r) / 2, ``"signed hybrid"`` max(r, 0) or
         ``"raw"`` r itself.
     power: the soft-threshold exponent, >= 1 (``"raw"`` layers, which may be negative, take 1).
+    threshold, top_percent_keep, binarize: the reference's ``network_transform``
+        (``preprocessing_utils.py:116-141``) applied to the finished layer, on the GPU
+        (``n2v2r_transform_layer``): entries below ``threshold`` are dropped, then only the top
+        ``top_percent_keep`` percent of the non-zero entries stay (an ``np.percentile`` cut), and
+        with ``binarize`` the survivors become 1.  The defaults (``None``, 100, ``False``) leave
+        the layer as built.  There is no ``absolute`` option: ``kind="unsigned"`` is that.
 
     Every violation is a ``ValueError`` here, before any GPU work; rows the correlation is
     undefined for (a non-finite value, zero variance) are reported by the engine when the layer
     is loaded, by row index."""
 
-    def __init__(self, expression, kind: str = "unsigned", power: float = 1.0):
+    def __init__(self, expression, kind: str = "unsigned", power: float = 1.0, threshold=None,
+                 top_percent_keep=100, binarize: bool = False):
         values = getattr(expression, "values", expression)  # (a DataFrame's array)
         try:
             e = np.ascontiguousarray(np.asarray(values), dtype=np.float64)
@@ -49,8 +56,27 @@ class Coexpression:
         self.kind = kind.replace("_", " ").casefold()
         if self.kind == "raw" and p != 1.0:
             raise ValueError("a raw correlation layer takes power 1 (r may be negative)")
+        if threshold is not None:
+            try:
+                threshold = float(threshold)
+            except (TypeError, ValueError):
+                raise ValueError(f"threshold must be a number or None, got {threshold!r}") from None
+            if not math.isfinite(threshold):
+                raise ValueError(f"threshold must be finite, got {threshold!r}")
+        try:
+            top = float(top_percent_keep)
+        except (TypeError, ValueError):
+            raise ValueError("top_percent_keep must be a number, got "
+                             f"{top_percent_keep!r}") from None
+        if not math.isfinite(top) or not 0.0 <= top <= 100.0:
+            raise ValueError(f"top_percent_keep must lie in [0, 100], got {top_percent_keep!r}")
+        if not isinstance(binarize, (bool, np.bool_)):
+            raise ValueError(f"binarize must be True or False, got {binarize!r}")
         self.expression = e
         self.power = p
+        self.threshold = threshold
+        self.top_percent_keep = top
+        self.binarize = bool(binarize)
 
     @property
     def shape(self):
@@ -61,6 +87,16 @@ class Coexpression:
     def kind_id(self) -> int:
         return KINDS[self.kind]
 
+    @property
+    def transforms(self) -> bool:
+        """Whether any of threshold / top_percent_keep / binarize is set."""
+        return self.threshold is not None or self.top_percent_keep != 100.0 or self.binarize
+
     def __repr__(self):
         n, s = self.expression.shape
-        return f"Coexpression(n={n}, samples={s}, kind={self.kind!r}, power={self.power:g})"
+        extra = ""
+        if self.transforms:
+            extra = (f", threshold={self.threshold!r}, top_percent_keep={self.top_percent_keep:g}"
+                     f", binarize={self.binarize}")
+        return (f"Coexpression(n={n}, samples={s}, kind={self.kind!r}, power={self.power:g}"
+                f"{extra})")

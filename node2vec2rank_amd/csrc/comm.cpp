@@ -45,6 +45,10 @@ struct RcclComm : Comm {
     op("ncclAllReduce(u64 max)",
        [&] { return ncclAllReduce(buf, buf, count, ncclUint64, ncclMax, c, st); });
   }
+  void allreduce_sum_u64(unsigned long long* buf, size_t count, hipStream_t st) override {
+    op("ncclAllReduce(u64 sum)",
+       [&] { return ncclAllReduce(buf, buf, count, ncclUint64, ncclSum, c, st); });
+  }
   void allreduce_sum_f32(float* buf, size_t count, hipStream_t st) override {
     op("ncclAllReduce(f32 sum)",
        [&] { return ncclAllReduce(buf, buf, count, ncclFloat, ncclSum, c, st); });
@@ -101,6 +105,9 @@ struct ThreadComm : Comm {
   void allreduce_max_u64(unsigned long long* buf, size_t count, hipStream_t st) override {
     allreduce(buf, count, st,
               [](unsigned long long a, unsigned long long b) { return a > b ? a : b; });
+  }
+  void allreduce_sum_u64(unsigned long long* buf, size_t count, hipStream_t st) override {
+    allreduce(buf, count, st, [](unsigned long long a, unsigned long long b) { return a + b; });
   }
   void allreduce_sum_f32(float* buf, size_t count, hipStream_t st) override {
     allreduce(buf, count, st, [](float a, float b) { return a + b; });

@@ -144,6 +144,13 @@ hipError_t n2v2r_launch_corr_standardise(const double* E, int64_t n, int64_t s, 
 hipError_t n2v2r_launch_corr_tiles(const double* Z, int64_t s, int64_t n, int64_t row0,
                                    int64_t nloc, float* A, int64_t lda, int kind, double power,
                                    hipStream_t stream);
+// transform.hip: threshold / top-percent / binarize of a dense layer in place
+hipError_t n2v2r_launch_tf_hist(const float* A, int64_t count, int absolute, float lim, int pass,
+                                uint32_t prefix, unsigned long long* out, hipStream_t stream);
+hipError_t n2v2r_launch_tf_min(const float* A, int64_t count, int absolute, float lim,
+                               uint32_t xkey, unsigned long long* out, hipStream_t stream);
+hipError_t n2v2r_launch_tf_apply(float* A, int64_t count, int absolute, float lim, int binarize,
+                                 unsigned long long* kept, hipStream_t stream);
 hipError_t n2v2r_launch_transpose(const float* in, int64_t ldi, int64_t rows, int64_t cols,
                                   float* out, int64_t ldo, hipStream_t stream);
 hipError_t n2v2r_launch_mismatch(const float* a, const float* b, int64_t ld, int64_t rows,
@@ -385,6 +392,7 @@ struct Comm {
   virtual void allgather(const void* send, void* recv, size_t bytes, hipStream_t st) = 0;
   virtual void allreduce_sum_f64(double* buf, size_t count, hipStream_t st) = 0;
   virtual void allreduce_max_u64(unsigned long long* buf, size_t count, hipStream_t st) = 0;
+  virtual void allreduce_sum_u64(unsigned long long* buf, size_t count, hipStream_t st) = 0;
   virtual void allreduce_sum_f32(float* buf, size_t count, hipStream_t st) = 0;
   // recv (count floats) = sum over ranks of their send[rank * count .. (rank + 1) * count)
   virtual void reduce_scatter_sum_f32(const float* send, float* recv, size_t count,
@@ -571,6 +579,7 @@ struct n2v2r_handle {
   // flags) and the embedding's panel slice, kept across calls (a per-call hipMalloc + zero
   // fill + device sync + hipFree each time otherwise)
   DevBuf ing_keys[2], ing_pay[2], ing_hist, ing_flag;
+  DevBuf tf_scr;  // n2v2r_transform_layer: digit histogram, NaN count, min key, survivors (u64)
   DevBuf ypanel;
 
 
@@ -752,6 +761,8 @@ int multi_set_layer_csr(n2v2r_handle* h, int k, int64_t n, int64_t nnz, const in
 int multi_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int symmetric);
 int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, const double* E,
                          int kind, double power);
+int multi_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
+                          double top_percent_keep, n2v2r_transform_stats* stats);
 int multi_get_layer_dense(n2v2r_handle* h, int k, float* A);
 int multi_column_sums(n2v2r_handle* h, int k, float* out);
 int multi_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_stats* stats);

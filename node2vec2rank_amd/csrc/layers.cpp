@@ -659,6 +659,211 @@ int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, con
   });
 }
 
+// the smallest fp32 >= v (v not NaN): for fp32 a, a >= tf_ceil32(v) exactly when !(a < v) in fp64
+static float tf_ceil32(double v) {
+  float f = (float)v;  // (round to nearest; +-inf beyond the fp32 range)
+  if ((double)f < v) f = std::nextafterf(f, INFINITY);
+  return f;
+}
+static double tf_key_value(uint32_t key) {
+  const uint32_t bits = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
+  float f;
+  std::memcpy(&f, &bits, sizeof(f));
+  return (double)f;
+}
+
+// one histogram pass of the radix select over this handle's rows, summed over the ranks:
+// host[0 .. 255] the digit counts, host[256] the NaNs (pass 0)
+static void tf_hist_pass(n2v2r_handle* h, const float* A, int64_t count, int absolute, float lim,
+                         int pass, uint32_t prefix, unsigned long long* host) {
+  unsigned long long* scr = h->tf_scr.as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(scr, 0, sizeof(unsigned long long) * 257, h->stream));
+  HIPCHK(n2v2r_launch_tf_hist(A, count, absolute, lim, pass, prefix, scr, h->stream));
+  if (h->comm) h->comm->allreduce_sum_u64(scr, 257, h->stream);
+  HIPCHK(hipMemcpyAsync(host, scr, sizeof(unsigned long long) * 257, hipMemcpyDeviceToHost,
+                        h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+}
+
+// network_transform of a dense layer in place (transform.hip).  Nothing is written before the
+// cut is known: the threshold is a predicate of the select passes.  Every decision below is taken
+// on numbers already reduced over the ranks, so all ranks of a partitioned handle take the same
+// one (the error returns included) and run the same collectives.
+int n2v2r_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
+                          double top_percent_keep, n2v2r_transform_stats* stats) {
+  if (h && h->multi())
+    return multi_transform_layer(h, k, flags, threshold, top_percent_keep, stats);
+  return guarded(h, [&]() -> int {
+    if (k < 0 || k >= h->K || !h->layers[k]->loaded) {
+      h->set_err("transform_layer: layer %d is not loaded", k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    LayerDev& L = *h->layers[k];
+    if (!L.dense) {
+      h->set_err("transform_layer: layer %d is stored as CSR; transform sparse layers on the host "
+                 "with node2vec2rank_amd.ingest.transform before loading them", k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (flags & ~(N2V2R_TF_ABSOLUTE | N2V2R_TF_BINARIZE | N2V2R_TF_THRESHOLD)) {
+      h->set_err("transform_layer: unknown flag bits in %d", flags);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (!std::isfinite(top_percent_keep) || top_percent_keep < 0.0 || top_percent_keep > 100.0) {
+      h->set_err("transform_layer: top_percent_keep must lie in [0, 100], got %g",
+                 top_percent_keep);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    const bool thr = (flags & N2V2R_TF_THRESHOLD) != 0;
+    if (thr && std::isnan(threshold)) {
+      h->err = "transform_layer: the threshold is NaN";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    const int absolute = (flags & N2V2R_TF_ABSOLUTE) ? 1 : 0;
+    const float lim = thr ? tf_ceil32(threshold) : -INFINITY;
+    hipStream_t st = h->stream;
+    const float* A = L.dA.as<float>();
+    const int64_t count = h->nloc * L.lda;
+    // [0, 256) digit counts, [256] NaNs, [257] complemented min key, [258] survivors
+    h->tf_scr.ensure_raw(sizeof(unsigned long long) * 260);
+    unsigned long long* scr = h->tf_scr.as<unsigned long long>();
+    unsigned long long host[260];
+
+    int64_t m = 0, lo = 0, hi = 0, rank = 0, below = 0;
+    double g = 0.0;
+    uint32_t prefix = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+      tf_hist_pass(h, A, count, absolute, lim, pass, prefix, host);
+      if (pass == 0) {
+        if (host[256]) {
+          h->set_err("transform_layer: layer %d holds %llu NaN entries", k, host[256]);
+          return N2V2R_ERR_BAD_ARG;
+        }
+        for (int b = 0; b < 256; ++b) m += (int64_t)host[b];
+        if (m == 0) {
+          h->set_err("transform_layer: layer %d has no non-zero entry left%s", k,
+                     thr ? " at this threshold" : "");
+          return N2V2R_ERR_BAD_ARG;
+        }
+        // np.percentile's "linear" method
+        const double q = 100.0 - top_percent_keep;
+        const double pos = (double)(m - 1) * (q / 100.0);
+        lo = std::min<int64_t>((int64_t)std::floor(pos), m - 1);
+        g = pos - (double)lo;
+        hi = std::min<int64_t>(lo + 1, m - 1);
+        rank = lo;
+      }
+      int b = 0;
+      for (; b < 255 && rank >= (int64_t)host[b]; ++b) {
+        rank -= (int64_t)host[b];
+        below += (int64_t)host[b];
+      }
+      if (rank >= (int64_t)host[b]) {
+        h->err = "transform_layer: the digit histogram does not hold the order statistic";
+        return N2V2R_ERR_INTERNAL;
+      }
+      prefix = (prefix << 8) | (uint32_t)b;
+      if (pass == 3) below += (int64_t)host[b];  // now: the alive entries <= x
+    }
+    const uint32_t xkey = prefix;
+    uint32_t ykey = xkey;
+    if (hi > lo && below <= lo + 1) {  // the hi-th smallest lies above x
+      HIPCHK(hipMemsetAsync(scr + 257, 0, sizeof(unsigned long long), st));
+      HIPCHK(n2v2r_launch_tf_min(A, count, absolute, lim, xkey, scr + 257, st));
+      if (h->comm) h->comm->allreduce_max_u64(scr + 257, 1, st);
+      HIPCHK(hipMemcpyAsync(host, scr + 257, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                            st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (host[0] == 0 || host[0] > 0xFFFFFFFFull) {
+        h->err = "transform_layer: no alive entry above the first order statistic";
+        return N2V2R_ERR_INTERNAL;
+      }
+      ykey = ~(uint32_t)host[0];
+    }
+    const double x = tf_key_value(xkey), y = tf_key_value(ykey), d = y - x;
+    const double cut = g < 0.5 ? x + d * g : y - d * (1.0 - g);
+    // `a < cut` is false for a NaN cut (infinite order statistics): nothing more dies
+    const float lim2 = std::isnan(cut) ? lim : std::max(lim, tf_ceil32(cut));
+
+    h->have_embedding = false;
+    HIPCHK(hipMemsetAsync(scr + 258, 0, sizeof(unsigned long long), st));
+    HIPCHK(n2v2r_launch_tf_apply(L.dA.as<float>(), count, absolute, lim2,
+                                 (flags & N2V2R_TF_BINARIZE) ? 1 : 0, scr + 258, st));
+    if (!L.symmetric)
+      HIPCHK(n2v2r_launch_tf_apply(L.dAT.as<float>(), count, absolute, lim2,
+                                   (flags & N2V2R_TF_BINARIZE) ? 1 : 0, nullptr, st));
+    if (h->comm) h->comm->allreduce_sum_u64(scr + 258, 1, st);
+    HIPCHK(hipMemcpyAsync(host, scr + 258, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats) {
+      stats->nonzero = m;
+      stats->kept = (int64_t)host[0];
+      stats->cut = cut;
+    }
+    return N2V2R_OK;
+  });
+}
+
+// diagnostics (n2v2r_diag.h): one kernel of the transform alone, timed with HIP events
+int n2v2r_bench_transform_pass(n2v2r_handle* h, int k, int which, int flags, double threshold,
+                               int reps, double* avg_ms, double* bytes) {
+  return guarded(h, [&]() -> int {
+    if (h->multi() || h->comm || k < 0 || k >= h->K || !h->layers[k]->loaded ||
+        !h->layers[k]->dense || which < 0 || which > 5 || reps < 1 || !avg_ms ||
+        ((flags & N2V2R_TF_THRESHOLD) && std::isnan(threshold))) {
+      h->err = "bench_transform_pass: a loaded dense layer of a one-GPU handle, which in [0, 5], "
+               "reps >= 1";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    LayerDev& L = *h->layers[k];
+    const int absolute = (flags & N2V2R_TF_ABSOLUTE) ? 1 : 0;
+    const float lim = (flags & N2V2R_TF_THRESHOLD) ? tf_ceil32(threshold) : -INFINITY;
+    hipStream_t st = h->stream;
+    float* A = L.dA.as<float>();
+    const int64_t count = h->nloc * L.lda;
+    h->tf_scr.ensure_raw(sizeof(unsigned long long) * 260);
+    unsigned long long* scr = h->tf_scr.as<unsigned long long>();
+    unsigned long long host[260];
+    // the digits of the median alive key, as far as the timed pass needs them
+    uint32_t prefix = 0;
+    int64_t rank = 0;
+    for (int pass = 0; pass < std::min(which, 4); ++pass) {
+      tf_hist_pass(h, A, count, absolute, lim, pass, prefix, host);
+      if (pass == 0) {
+        int64_t m = 0;
+        for (int b = 0; b < 256; ++b) m += (int64_t)host[b];
+        rank = m / 2;
+      }
+      int b = 0;
+      for (; b < 255 && rank >= (int64_t)host[b]; ++b) rank -= (int64_t)host[b];
+      prefix = (prefix << 8) | (uint32_t)b;
+    }
+    auto launch = [&]() {
+      if (which < 4) return n2v2r_launch_tf_hist(A, count, absolute, lim, which, prefix, scr, st);
+      if (which == 4) return n2v2r_launch_tf_min(A, count, absolute, lim, prefix, scr + 257, st);
+      return n2v2r_launch_tf_apply(A, count, 0, -INFINITY, 0, scr + 258, st);
+    };
+    HIPCHK(hipMemsetAsync(scr, 0, sizeof(unsigned long long) * 260, st));
+    HIPCHK(launch());
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    // one event pair around `reps` launches back to back, as tools/stream_ceiling.hip times its
+    // kernels (the counts just keep adding up: nothing reads them)
+    hipError_t err = hipEventRecord(e0, st);
+    for (int r = 0; r < reps && err == hipSuccess; ++r) err = launch();
+    if (err == hipSuccess) err = hipEventRecord(e1, st);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (err != hipSuccess) throw HipFail{err, "bench_transform_pass"};
+    *avg_ms = (double)ms / reps;
+    if (bytes) *bytes = 4.0 * (double)count;
+    return N2V2R_OK;
+  });
+}
+
 // diagnostics (n2v2r_diag.h): a dense layer's rows back on the host
 int n2v2r_get_layer_dense(n2v2r_handle* h, int k, float* A) {
   if (h && h->multi()) return multi_get_layer_dense(h, k, A);

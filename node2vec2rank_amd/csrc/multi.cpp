@@ -247,6 +247,17 @@ int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, con
   });
 }
 
+// collective inside: every rank selects over the summed histograms and returns the global stats
+int multi_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
+                          double top_percent_keep, n2v2r_transform_stats* stats) {
+  std::vector<n2v2r_transform_stats> rs(h->ranks.size());
+  const int st = fanout(h, [&](n2v2r_handle* r, int i) {
+    return n2v2r_transform_layer(r, k, flags, threshold, top_percent_keep, &rs[i]);
+  });
+  if (st == N2V2R_OK && stats) *stats = rs[0];
+  return st;
+}
+
 // rank r's rows land at row0 of the caller's n x n array (disjoint bands)
 int multi_get_layer_dense(n2v2r_handle* h, int k, float* A) {
   if (!A) {
