@@ -244,6 +244,33 @@ enum { N2V2R_TF_ABSOLUTE = 1, N2V2R_TF_BINARIZE = 2, N2V2R_TF_THRESHOLD = 4 };
 typedef struct { int64_t nonzero; int64_t kept; double cut; } n2v2r_transform_stats;
 int n2v2r_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
                           double top_percent_keep, n2v2r_transform_stats* stats /* may be NULL */);
+/* Topological overlap (WGCNA's TOMsimilarity with TOMDenom = "min", hdWGCNA's GetTOM) of a loaded
+ * SYMMETRIC DENSE-storage layer, in HBM, whichever call loaded it: the layer never visits the
+ * host.  With a = the stored fp32 values as fp64 (exact) and a0 = a with its diagonal replaced
+ * by 0 (the stored diagonal is ignored):
+ *   N2V2R_TOM_UNSIGNED: k_i = sum_u a0[i,u], L_ij = sum_u a0[i,u] a0[u,j],
+ *                       T_ij = (L_ij + a0_ij) / (min(k_i, k_j) + 1 - a0_ij);
+ *   N2V2R_TOM_SIGNED (layers that may be negative, N2V2R_CORR_RAW): k_i = sum_u |a0[i,u]|,
+ *                       T_ij = |L_ij + a0_ij| / (min(k_i, k_j) + 1 - |a0_ij|);
+ *   T_ii = 1.  (The denominator is >= 1 for a layer inside the type's range.)
+ * L is one fp64 MFMA product over the upper-triangle tiles (the layer's fp32 rows widened to fp64
+ * on their way into LDS, the diagonal masked there), k_i an fp64 row sum, the formula is
+ * evaluated per entry in fp64 and rounded ONCE to fp32; the result is bit-exactly symmetric and
+ * the padding columns stay +0.  It goes to a scratch buffer of the layer's size that then changes
+ * places with the layer's buffer (no copy; the old buffer is the scratch of the next call), so
+ * the handle holds one extra layer-sized buffer after the first call.
+ * On a partitioned handle the call is collective: the row bands are all-gathered into a full
+ * n x n copy on every rank (4 n^2 bytes, freed when the call returns), every rank computes the
+ * tiles that meet its band and gets the bits one GPU gets, and the validation counts are summed
+ * over the ranks, so every rank returns the same status.
+ * The call clears the embedding (n2v2r_uase has to run again).
+ * N2V2R_ERR_BAD_ARG, layer untouched (one validation pass runs before anything is written, so the
+ * call can be repeated): a layer that is not loaded; a CSR-storage layer; a directed layer (one
+ * that keeps an A^T copy: the overlap is defined for symmetric adjacencies); an unknown type; a
+ * NaN in the layer; a value outside [0, 1] (N2V2R_TOM_UNSIGNED) or [-1, 1] (N2V2R_TOM_SIGNED),
+ * diagonal included -- the message names the count of either. */
+enum { N2V2R_TOM_UNSIGNED = 0, N2V2R_TOM_SIGNED = 1 };
+int n2v2r_tom_layer(n2v2r_handle* h, int k, int type);
 /* distributed ingest without the global CSR on every rank: the caller's own rows
  * [row0, row0 + n_rows) (must equal n2v2r_dist_info's) of a SYMMETRIC layer, indptr local
  * (starting at 0), column indices global. */

@@ -71,6 +71,14 @@ int n2v2r_get_layer_dense(n2v2r_handle* h, int k, float* A /* n x n */);
 int n2v2r_bench_transform_pass(n2v2r_handle* h, int k, int which, int flags, double threshold,
                                int reps, double* avg_ms, double* bytes);
 
+/* tom_tile_kernel of n2v2r_tom_layer alone on the loaded symmetric dense layer k of a one-GPU
+ * handle (tools/tom_probe.py): the row sums once, one warm-up launch, then `reps` launches into
+ * the handle's scratch buffer, each between its own HIP event pair on the engine stream; the
+ * layer is left as it is.  ms[0 .. reps) = the launches' times; flop (optional) = what one launch
+ * computes: 2 * 64 * 64 * lda for each of the nt (nt + 1) / 2 upper-triangle tiles, nt = lda / 64,
+ * lda = 64 ceil(n / 64) (about n^3). */
+int n2v2r_bench_tom_tiles(n2v2r_handle* h, int k, int type, int reps, double* ms, double* flop);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,7 +52,7 @@ EXPORTED = [
     "n2v2r_rr_top", "n2v2r_rr_band_top", "n2v2r_set_layer_dense", "n2v2r_project",
     "n2v2r_create_multi", "n2v2r_multi_devices", "n2v2r_h2d_layer_bytes",
     "n2v2r_set_layer_corr", "n2v2r_get_layer_dense", "n2v2r_transform_layer",
-    "n2v2r_bench_transform_pass",
+    "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -96,6 +96,8 @@ class TransformStats(ctypes.Structure):
 
 # n2v2r_transform_layer flags (include/n2v2r.h)
 TF_ABSOLUTE, TF_BINARIZE, TF_THRESHOLD = 1, 2, 4
+# n2v2r_tom_layer types: N2V2R_TOM_*
+TOM_KINDS = {"unsigned": 0, "signed": 1}
 
 _lib = None
 _lock = threading.RLock()  # re-entered: acquire_engine -> Engine() -> load()
@@ -181,6 +183,9 @@ def load(path: str | None = None):
             "n2v2r_bench_transform_pass": (_i, [_vp, _i, _i, _i, ctypes.c_double, _i,
                                                 ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_double)]),
+            "n2v2r_tom_layer": (_i, [_vp, _i, _i]),
+            "n2v2r_bench_tom_tiles": (_i, [_vp, _i, _i, _i, _p(np.float64),
+                                           ctypes.POINTER(ctypes.c_double)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -386,7 +391,11 @@ class Engine:
                 else:
                     st = self.lib.n2v2r_set_layer_dense(self.h, k, n, a, int(symmetric))
                 self._check(st, f"layer {k}")
-                if isinstance(a, Coexpression) and a.transforms:
+                # WGCNA's order (adjacency, then its topological overlap), then the reference's
+                # network_transform
+                if isinstance(a, Coexpression) and a.tom is not None:
+                    self.tom_layer(k, kind=a.tom)
+                if isinstance(a, Coexpression) and a.filters:
                     self.transform_layer(k, threshold=a.threshold,
                                          top_percent_keep=a.top_percent_keep,
                                          binarize=a.binarize)
@@ -604,6 +613,27 @@ class Engine:
         self._check(self.lib.n2v2r_transform_layer(self.h, int(k), flags, thr, top,
                                                    ctypes.byref(st)), f"transform_layer {k}")
         return {"nonzero": int(st.nonzero), "kept": int(st.kept), "cut": float(st.cut)}
+
+    def tom_layer(self, k: int, kind: str = "unsigned"):
+        """Replace the loaded symmetric dense-storage layer k by its topological overlap matrix
+        on the GPU (n2v2r_tom_layer): WGCNA's ``TOMsimilarity`` with ``TOMDenom="min"``, fp64
+        rounded once to fp32, the layer's diagonal ignored and the result's set to 1.  kind:
+        ``"unsigned"`` (entries in [0, 1]) or ``"signed"`` (entries in [-1, 1], a ``"raw"``
+        co-expression layer).  ``ValueError`` (layer untouched): an unknown kind, a layer that
+        is not loaded, CSR-stored or directed, a NaN or a value outside the kind's range."""
+        if not isinstance(kind, str) or kind.casefold() not in TOM_KINDS:
+            raise ValueError(f"unknown TOM kind {kind!r}; options are {sorted(TOM_KINDS)}")
+        self._check(self.lib.n2v2r_tom_layer(self.h, int(k), TOM_KINDS[kind.casefold()]),
+                    f"tom_layer {k}")
+
+    def bench_tom_tiles(self, k: int, kind: str = "unsigned", reps: int = 5):
+        """Time the tile kernel of ``tom_layer`` alone (n2v2r_bench_tom_tiles; the layer stays as
+        it is).  Returns (the launches' ms as an array, the flop of one launch)."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        flop = ctypes.c_double()
+        self._check(self.lib.n2v2r_bench_tom_tiles(self.h, int(k), TOM_KINDS[kind], int(reps), ms,
+                                                   ctypes.byref(flop)), "bench_tom_tiles")
+        return ms, flop.value
 
     def bench_transform_pass(self, k: int, which: int, threshold=None, absolute=False,
                              reps: int = 20):

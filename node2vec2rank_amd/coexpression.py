@@ -12,6 +12,8 @@ import numpy as np
 
 # kind -> N2V2R_CORR_* (include/n2v2r.h); the names follow WGCNA's networkType
 KINDS = {"unsigned": 0, "signed": 1, "signed hybrid": 2, "raw": 3}
+# tom -> N2V2R_TOM_*; the names follow WGCNA's TOMType
+TOMS = ("unsigned", "signed")
 
 
 class Coexpression:
@@ -22,6 +24,12 @@ class Coexpression:
     kind: ``"unsigned"`` |r|, ``"signed"`` (1 + r) / 2, ``"signed hybrid"`` max(r, 0) or
         ``"raw"`` r itself.
     power: the soft-threshold exponent, >= 1 (``"raw"`` layers, which may be negative, take 1).
+    tom: ``None`` (the adjacency itself), ``"unsigned"`` or ``"signed"``: the layer becomes the
+        topological overlap matrix of the adjacency (WGCNA's ``TOMsimilarity`` with
+        ``TOMDenom="min"``, hdWGCNA's ``GetTOM``), on the GPU (``n2v2r_tom_layer``), before the
+        options below.  ``"unsigned"`` needs entries in [0, 1] (every kind but ``"raw"`` gives
+        them); ``"signed"`` takes [-1, 1].  The engine checks the range when the layer is
+        loaded: a ``"raw"`` layer that happens to be non-negative passes as ``"unsigned"``.
     threshold, top_percent_keep, binarize: the reference's ``network_transform``
         (``preprocessing_utils.py:116-141``) applied to the finished layer, on the GPU
         (``n2v2r_transform_layer``): entries below ``threshold`` are dropped, then only the top
@@ -34,7 +42,7 @@ class Coexpression:
     is loaded, by row index."""
 
     def __init__(self, expression, kind: str = "unsigned", power: float = 1.0, threshold=None,
-                 top_percent_keep=100, binarize: bool = False):
+                 top_percent_keep=100, binarize: bool = False, tom=None):
         values = getattr(expression, "values", expression)  # (a DataFrame's array)
         try:
             e = np.ascontiguousarray(np.asarray(values), dtype=np.float64)
@@ -72,11 +80,14 @@ class Coexpression:
             raise ValueError(f"top_percent_keep must lie in [0, 100], got {top_percent_keep!r}")
         if not isinstance(binarize, (bool, np.bool_)):
             raise ValueError(f"binarize must be True or False, got {binarize!r}")
+        if tom is not None and (not isinstance(tom, str) or tom.casefold() not in TOMS):
+            raise ValueError(f"unknown tom {tom!r}; options are None, 'unsigned' and 'signed'")
         self.expression = e
         self.power = p
         self.threshold = threshold
         self.top_percent_keep = top
         self.binarize = bool(binarize)
+        self.tom = None if tom is None else tom.casefold()
 
     @property
     def shape(self):
@@ -88,15 +99,23 @@ class Coexpression:
         return KINDS[self.kind]
 
     @property
-    def transforms(self) -> bool:
+    def filters(self) -> bool:
         """Whether any of threshold / top_percent_keep / binarize is set."""
         return self.threshold is not None or self.top_percent_keep != 100.0 or self.binarize
+
+    @property
+    def transforms(self) -> bool:
+        """Whether the layer is changed after the correlation build: ``tom`` or any of
+        threshold / top_percent_keep / binarize."""
+        return self.tom is not None or self.filters
 
     def __repr__(self):
         n, s = self.expression.shape
         extra = ""
-        if self.transforms:
-            extra = (f", threshold={self.threshold!r}, top_percent_keep={self.top_percent_keep:g}"
-                     f", binarize={self.binarize}")
+        if self.tom is not None:
+            extra = f", tom={self.tom!r}"
+        if self.filters:
+            extra += (f", threshold={self.threshold!r}, top_percent_keep={self.top_percent_keep:g}"
+                      f", binarize={self.binarize}")
         return (f"Coexpression(n={n}, samples={s}, kind={self.kind!r}, power={self.power:g}"
                 f"{extra})")

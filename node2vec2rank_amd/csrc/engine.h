@@ -144,6 +144,15 @@ hipError_t n2v2r_launch_corr_standardise(const double* E, int64_t n, int64_t s, 
 hipError_t n2v2r_launch_corr_tiles(const double* Z, int64_t s, int64_t n, int64_t row0,
                                    int64_t nloc, float* A, int64_t lda, int kind, double power,
                                    hipStream_t stream);
+// tom.hip: topological overlap of a symmetric dense layer.  A: all n rows of the layer (n x lda
+// fp32); type: N2V2R_TOM_*
+hipError_t n2v2r_launch_tom_check(const float* A, int64_t rows, int64_t lda, int64_t n, int type,
+                                  unsigned long long* counts, hipStream_t stream);
+hipError_t n2v2r_launch_tom_rowsum(const float* A, int64_t lda, int64_t n, int type, double* ksum,
+                                   hipStream_t stream);
+hipError_t n2v2r_launch_tom_tiles(const float* A, int64_t lda, int64_t n, const double* ksum,
+                                  int type, int64_t row0, int64_t nloc, float* T,
+                                  hipStream_t stream);
 // transform.hip: threshold / top-percent / binarize of a dense layer in place
 hipError_t n2v2r_launch_tf_hist(const float* A, int64_t count, int absolute, float lim, int pass,
                                 uint32_t prefix, unsigned long long* out, hipStream_t stream);
@@ -309,6 +318,10 @@ struct DevBuf {
                        "hipMalloc of " + std::to_string(b) + " bytes failed"};
     }
     bytes = b;
+  }
+  void swap(DevBuf& o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
   }
   template <class T>
   T* as() const {
@@ -580,6 +593,7 @@ struct n2v2r_handle {
   // fill + device sync + hipFree each time otherwise)
   DevBuf ing_keys[2], ing_pay[2], ing_hist, ing_flag;
   DevBuf tf_scr;  // n2v2r_transform_layer: digit histogram, NaN count, min key, survivors (u64)
+  DevBuf tom_out;  // n2v2r_tom_layer: the result, then swapped with the layer's dA (kept as scratch)
   DevBuf ypanel;
 
 
@@ -763,6 +777,7 @@ int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, con
                          int kind, double power);
 int multi_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
                           double top_percent_keep, n2v2r_transform_stats* stats);
+int multi_tom_layer(n2v2r_handle* h, int k, int type);
 int multi_get_layer_dense(n2v2r_handle* h, int k, float* A);
 int multi_column_sums(n2v2r_handle* h, int k, float* out);
 int multi_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_stats* stats);

@@ -803,6 +803,130 @@ int n2v2r_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
   });
 }
 
+// Topological overlap of a symmetric dense layer (tom.hip) into the handle's scratch buffer, which
+// then changes places with the layer's dA.  A partitioned rank gathers every band into a full
+// copy first (bands of npad rows, rank r's at row r npad = its row0; a shorter last band is sent
+// from a zero-padded staging copy) and computes the tiles that meet its own band.  Every decision
+// that is not the same on all ranks by construction (the counts, and whether some rank keeps an
+// A^T copy) is taken on numbers summed over the ranks, so all ranks return alike and run the same
+// collectives.
+int n2v2r_tom_layer(n2v2r_handle* h, int k, int type) {
+  if (h && h->multi()) return multi_tom_layer(h, k, type);
+  return guarded(h, [&]() -> int {
+    if (k < 0 || k >= h->K || !h->layers[k]->loaded) {
+      h->set_err("tom_layer: layer %d is not loaded", k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    LayerDev& L = *h->layers[k];
+    if (!L.dense) {
+      h->set_err("tom_layer: layer %d is stored as CSR; the topological overlap is dense: load "
+                 "the layer with dense storage", k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (type != N2V2R_TOM_UNSIGNED && type != N2V2R_TOM_SIGNED) {
+      h->set_err("tom_layer: unknown type %d", type);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    hipStream_t st = h->stream;
+    const int64_t n = h->n, lda = L.lda;
+    // [0] NaNs, [1] entries outside the type's range, [2] ranks that keep an A^T copy
+    h->tf_scr.ensure_raw(sizeof(unsigned long long) * 260);
+    unsigned long long* scr = h->tf_scr.as<unsigned long long>();
+    unsigned long long host[3] = {0, 0, L.symmetric ? 0ull : 1ull};
+    HIPCHK(hipMemcpyAsync(scr, host, sizeof(host), hipMemcpyHostToDevice, st));
+    HIPCHK(n2v2r_launch_tom_check(L.dA.as<float>(), h->nloc, lda, n, type, scr, st));
+    if (h->comm) h->comm->allreduce_sum_u64(scr, 3, st);
+    HIPCHK(hipMemcpyAsync(host, scr, sizeof(host), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (host[2]) {
+      h->set_err("tom_layer: layer %d is directed (it keeps an A^T copy); the topological overlap "
+                 "is defined for symmetric adjacencies", k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (host[0]) {
+      h->set_err("tom_layer: layer %d holds %llu NaN entries", k, host[0]);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (host[1]) {
+      h->set_err("tom_layer: layer %d holds %llu entries outside the range %s of the %s overlap",
+                 k, host[1], type == N2V2R_TOM_SIGNED ? "[-1, 1]" : "[0, 1]",
+                 type == N2V2R_TOM_SIGNED ? "signed" : "unsigned");
+      return N2V2R_ERR_BAD_ARG;
+    }
+    DevBuf full, stage, ksum;
+    const float* A = L.dA.as<float>();
+    if (h->comm) {
+      const size_t band = sizeof(float) * (size_t)h->npad * lda;
+      full.ensure_raw(band * h->world);
+      const void* send = L.dA.p;
+      if (h->nloc < h->npad) {
+        stage.ensure(band, st);
+        if (h->nloc > 0)
+          HIPCHK(hipMemcpyAsync(stage.p, L.dA.p, sizeof(float) * (size_t)h->nloc * lda,
+                                hipMemcpyDeviceToDevice, st));
+        send = stage.p;
+      }
+      h->comm->allgather(send, full.p, band, st);
+      A = full.as<float>();
+    }
+    ksum.ensure_raw(sizeof(double) * n);
+    h->tom_out.ensure_raw(sizeof(float) * std::max<int64_t>(h->nloc, 1) * lda);
+    HIPCHK(n2v2r_launch_tom_rowsum(A, lda, n, type, ksum.as<double>(), st));
+    HIPCHK(n2v2r_launch_tom_tiles(A, lda, n, ksum.as<double>(), type, h->row0, h->nloc,
+                                  h->tom_out.as<float>(), st));
+    HIPCHK(hipStreamSynchronize(st));  // full, stage and ksum die here
+    h->have_embedding = false;
+    L.dA.swap(h->tom_out);
+    return N2V2R_OK;
+  });
+}
+
+// diagnostics (n2v2r_diag.h): tom_tile_kernel alone, one HIP event pair per launch
+int n2v2r_bench_tom_tiles(n2v2r_handle* h, int k, int type, int reps, double* ms, double* flop) {
+  return guarded(h, [&]() -> int {
+    if (h->multi() || h->comm || k < 0 || k >= h->K || !h->layers[k]->loaded ||
+        !h->layers[k]->dense || !h->layers[k]->symmetric || reps < 1 || !ms ||
+        (type != N2V2R_TOM_UNSIGNED && type != N2V2R_TOM_SIGNED)) {
+      h->err = "bench_tom_tiles: a loaded symmetric dense layer of a one-GPU handle, a known "
+               "type, reps >= 1";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    LayerDev& L = *h->layers[k];
+    hipStream_t st = h->stream;
+    const int64_t n = h->n;
+    DevBuf ksum;
+    ksum.ensure_raw(sizeof(double) * n);
+    h->tom_out.ensure_raw(sizeof(float) * n * L.lda);
+    HIPCHK(n2v2r_launch_tom_rowsum(L.dA.as<float>(), L.lda, n, type, ksum.as<double>(), st));
+    auto launch = [&]() {
+      return n2v2r_launch_tom_tiles(L.dA.as<float>(), L.lda, n, ksum.as<double>(), type, 0, n,
+                                    h->tom_out.as<float>(), st);
+    };
+    HIPCHK(launch());  // warm-up
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    hipError_t err = hipSuccess;
+    for (int r = 0; r < reps && err == hipSuccess; ++r) {
+      err = hipEventRecord(e0, st);
+      if (err == hipSuccess) err = launch();
+      if (err == hipSuccess) err = hipEventRecord(e1, st);
+      if (err == hipSuccess) err = hipEventSynchronize(e1);
+      float t = 0.f;
+      if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+      ms[r] = (double)t;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (err != hipSuccess) throw HipFail{err, "bench_tom_tiles"};
+    if (flop) {  // the tiles computed: the upper triangle of 64 x 64 tiles, k over all of lda
+      const double nt = (double)(L.lda / 64);
+      *flop = nt * (nt + 1.0) / 2.0 * 2.0 * 64.0 * 64.0 * (double)L.lda;
+    }
+    return N2V2R_OK;
+  });
+}
+
 // diagnostics (n2v2r_diag.h): one kernel of the transform alone, timed with HIP events
 int n2v2r_bench_transform_pass(n2v2r_handle* h, int k, int which, int flags, double threshold,
                                int reps, double* avg_ms, double* bytes) {

@@ -258,6 +258,11 @@ int multi_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
   return st;
 }
 
+// collective inside: the bands are all-gathered and the validation counts summed over the ranks
+int multi_tom_layer(n2v2r_handle* h, int k, int type) {
+  return fanout(h, [&](n2v2r_handle* r, int) { return n2v2r_tom_layer(r, k, type); });
+}
+
 // rank r's rows land at row0 of the caller's n x n array (disjoint bands)
 int multi_get_layer_dense(n2v2r_handle* h, int k, float* A) {
   if (!A) {
