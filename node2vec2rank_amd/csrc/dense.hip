@@ -16,6 +16,7 @@
 //           flagging rank-deficient columns; rows of those columns are refilled with
 //           random values by fill_flagged so the next CGS pass can orthogonalise them.
 #include "common.h"
+#include "pip_pass.h"
 
 // Breakdown handling of the Cholesky-QR passes.  The pivot p of column j is the squared norm of
 // Z_j - Q C_j by Pythagoras (Z_j^T Z_j - C_j^T C_j), which carries an error of ~1e-8 .. 1e-7 of
@@ -656,9 +657,7 @@ __global__ __launch_bounds__(256) void ts_tn_stream_lds_kernel(BlockList A, cons
 }
 
 // Gram-kernel selection for 8-wide blocks: the streaming form (about 4096 waves, chunks of at
-// least 256 rows); the line form where its partials would not fit (the A/B switch retired in
-// round 5)
-static bool tn_stream_form() { return true; }
+// least 256 rows); the line form where its partials would not fit
 #define TN_STREAM_WAVES 4096
 #define TN_STREAM_MIN_ROWS 256
 
@@ -667,7 +666,7 @@ static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n
                                const int* cond, const ZSum* zs, hipStream_t stream) {
   const int ca = A.count * A.width, cb = B.count * B.width;
   int64_t s_chunks = 0, s_rows = 0;
-  if (B.count == 1 && B.width == 8 && A.width == 8 && tn_stream_form()) {
+  if (B.count == 1 && B.width == 8 && A.width == 8) {
     // streaming form: ~TN_STREAM_WAVES (4096) waves, chunks of <= TS_MAX_CHUNK rows, nchunks % 8 == 0
     // (<= 4 blocks -- the local pass -- aim at half the waves: longer chunks, half the partials
     // to reduce; cfg4 Gram 30.1 -> 28.4 us and reduce 7.0 -> 5.0 us per pass, 1024 / 8192 worse;
@@ -1444,26 +1443,24 @@ static hipError_t launch_nn(const BlockList& A, const Coef& F, int cb, const Out
   return hipGetLastError();
 }
 
-// flags (nullptr = none): output columns j with flags[j] != 0 are written with N(0,1) deviates
-// (counter-based, seed) instead of the product: the refill of rank-deficient Krylov columns.
+// The plain product O = alpha A G + beta C: unconditional, no column refilled.
 extern "C" hipError_t n2v2r_launch_ts_nn(const BlockList& A, const float* G, int ldg, int cb,
                                          const OutBlockList& O, const BlockList& C, float alpha,
-                                         float beta, int64_t n, const int* cond,
-                                         const int* flags, uint64_t seed, hipStream_t stream) {
+                                         float beta, int64_t n, hipStream_t stream) {
   const Coef F{G, ldg, nullptr, nullptr, 0};
-  return launch_nn(A, F, cb, O, C, alpha, beta, n, cond, flags, seed, 0, stream);
+  return launch_nn(A, F, cb, O, C, alpha, beta, n, nullptr, nullptr, 0, 0, stream);
 }
 
 // Z <- [Q Z] F, F = [-C R^{-1}; R^{-1}] (fp32 (c + b) x b, formed by pip_chol): the fused
-// BCGS + CholQR apply.
+// BCGS + CholQR apply.  Output columns j with p.flags[j] != 0 are written with N(0,1) deviates
+// (counter-based, p.seed) instead of the product: the refill of rank-deficient Krylov columns.
 extern "C" hipError_t n2v2r_launch_pip_apply(const BlockList& QZ, const float* Fm, int c, int b,
-                                             const OutBlockList& Z, int64_t n, const int* cond,
-                                             const int* flags, uint64_t seed, int64_t row0,
+                                             const OutBlockList& Z, int64_t n, const PipPass& p,
                                              hipStream_t stream) {
   (void)c;
   const Coef F{Fm, b, nullptr, nullptr, 0};
   BlockList none{};
-  return launch_nn(QZ, F, b, Z, none, 1.f, 0.f, n, cond, flags, seed, row0, stream);
+  return launch_nn(QZ, F, b, Z, none, 1.f, 0.f, n, p.cond, p.flags, p.seed, p.row0, stream);
 }
 
 // ----------------------------------------------------------------------------- small ops
@@ -1861,18 +1858,15 @@ __global__ __launch_bounds__(1024) void pip_chol_kernel(const double* __restrict
 }
 
 extern "C" hipError_t n2v2r_launch_pip_chol(const double* G, int c, int b, double* xinv,
-                                            int* flags, int* any_flag, const int* cond,
-                                            double* save, int save_row0, int save_rows,
-                                            float* fout, int* sticky, double* rsave,
-                                            int first, hipStream_t stream) {
+                                            float* fout, const PipPass& p, hipStream_t stream) {
   if (b > 64) return hipErrorInvalidValue;
   const size_t gbytes = sizeof(double) * (size_t)(c + b) * b;
   const int stage = gbytes <= 56 * 1024 ? 1 : 0;
   // wide blocks with F wanted: F's rows over up to 8 workgroups (each factors P itself)
   const int nwg = (fout && b > 8) ? std::min(8, (c + b + 127) / 128) : 1;
   hipLaunchKernelGGL(pip_chol_kernel, dim3(nwg), dim3(1024), stage ? gbytes : 0, stream, G, c, b,
-                     xinv, flags, any_flag, cond, save, save_row0, save_rows, fout, stage, sticky,
-                     rsave, first);
+                     xinv, p.flags, p.any_flag, p.cond, p.save, p.save_row0, p.save_rows, fout,
+                     stage, p.sticky, p.rsave, p.first);
   return hipGetLastError();
 }
 
@@ -2204,15 +2198,11 @@ __global__ __launch_bounds__(256) void pip_fused_kernel(BlockList Q, const float
 }
 
 extern "C" hipError_t n2v2r_launch_pip_fused(const BlockList& Q, const float* Zin, float* Zout,
-                                             const double* G, int c, int64_t n, const int* cond,
-                                             int* flags, int* any_flag, double* save,
-                                             int save_row0, int save_rows, int* sticky,
-                                             uint64_t seed, int64_t row0, double* rsave,
-                                             float skip_tol, int* skipped, int first,
+                                             const double* G, int c, int64_t n, const PipPass& p,
                                              hipStream_t stream) {
   if (Q.width != 8 || c != Q.count * 8) return hipErrorInvalidValue;
   // a skipped block leaves Z in place; the band save reads G before the skipped rows are zeroed
-  if (skip_tol != 0.f && (Zin != Zout || save)) return hipErrorInvalidValue;
+  if (p.skip_tol != 0.f && (Zin != Zout || p.save)) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * ((size_t)(c + 8) * 8 + 256) + sizeof(float) * ((size_t)c * 8 + 64) + 16 +
                      4 * (size_t)(c / 8 > 64 ? c / 8 : 64);
   if (lds > 80 * 1024 || c > N2V2R_BAND_MAXC) return hipErrorInvalidValue;
@@ -2238,8 +2228,8 @@ extern "C" hipError_t n2v2r_launch_pip_fused(const BlockList& Q, const float* Zi
   const unsigned grid = (unsigned)((n + rows - 1) / rows);
 #define PIP_LAUNCH(QB_, NU_, NT_)                                                                \
   hipLaunchKernelGGL((pip_fused_kernel<QB_, NU_, NT_>), dim3(grid ? grid : 1), dim3(256), lds, stream, Q, \
-                     Zin, Zout, G, c, n, cond, flags, any_flag, save, save_row0, save_rows, sticky,  \
-                     seed, row0, rsave, skip_tol, skipped, first)
+                     Zin, Zout, G, c, n, p.cond, p.flags, p.any_flag, p.save, p.save_row0,         \
+                     p.save_rows, p.sticky, p.seed, p.row0, p.rsave, p.skip_tol, p.skipped, p.first)
   const bool nt = basis_nt(n, Q.count);
   if (rows == 256) {
     if (nt) PIP_LAUNCH(4, 2, true); else PIP_LAUNCH(4, 2, false);

@@ -28,6 +28,7 @@
 #include "common.h"
 
 // ---- kernel launchers (spmm.hip, dense.hip, rank.hip) ------------------------------------
+#include "pip_pass.h"  // PipPass, the pass and Gram launchers (shared with the probes in tools/)
 #include "spmm_args.h"
 #define DIST_MAX_COLS 256
 struct DistPlan {
@@ -54,28 +55,17 @@ int64_t n2v2r_cb_scan_tiles(int64_t n, int nb);
 hipError_t n2v2r_launch_cb_fill(const CsrDev& A, int64_t cw, int nb, const int64_t* rp,
                                 int32_t* idx, float* dat, int cbits, int wbits,
                                 hipStream_t stream);
-hipError_t n2v2r_launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n, double* partial,
-                              size_t partial_elems, double* out, const int* cond,
-                              hipStream_t stream);
 hipError_t n2v2r_launch_ritz_nn(const BlockList& A0, const BlockList& A1, const float* G, int ldg,
                                 int cb, const OutBlockList& O0, const OutBlockList& O1, int64_t n,
                                 int grid, hipStream_t stream);
 hipError_t n2v2r_launch_ts_nn(const BlockList& A, const float* G, int ldg, int cb,
                               const OutBlockList& O, const BlockList& C, float alpha, float beta,
-                              int64_t n, const int* cond, const int* flags, uint64_t seed,
-                              hipStream_t stream);
-hipError_t n2v2r_launch_pip_chol(const double* G, int c, int b, double* xinv, int* flags,
-                                 int* any_flag, const int* cond, double* save, int save_row0,
-                                 int save_rows, float* fout, int* sticky, double* rsave,
-                                 int first, hipStream_t stream);
+                              int64_t n, hipStream_t stream);
 hipError_t n2v2r_launch_rr_band(const double* hband, int c, int kp, double* theta, double* AB,
                                 double* Varr, double* taua, double* d, double* e, double* refl,
                                 double* Y, float* S, int ldS, int p, int* err,
                                 hipStream_t stream);
 int n2v2r_rr_band_jm(int c);
-// b = 8 PIP passes use the fused Cholesky + apply launch (its A/B switch retired in round 5;
-// the two-launch form serves b > 8 and bases beyond 512 columns)
-inline bool pip_fused() { return true; }
 hipError_t n2v2r_launch_ts_tn2(const BlockList& A, const float* Za, const float* Zb, int64_t n,
                                double* partial, size_t partial_elems, double* out,
                                hipStream_t stream);
@@ -88,15 +78,6 @@ hipError_t n2v2r_launch_pip_pair(const BlockList& Q, float* Za, float* Zb, doubl
                                  int* flags, int* any_flag, int* sticky, uint64_t seed_a,
                                  uint64_t seed_b, int64_t row0, float skip_tol, int* skipped,
                                  int* plan, size_t plan_bytes, hipStream_t stream);
-hipError_t n2v2r_launch_pip_fused(const BlockList& Q, const float* Zin, float* Zout,
-                                  const double* G, int c, int64_t n, const int* cond, int* flags,
-                                  int* any_flag, double* save, int save_row0, int save_rows,
-                                  int* sticky, uint64_t seed, int64_t row0, double* rsave,
-                                  float skip_tol, int* skipped, int first, hipStream_t stream);
-hipError_t n2v2r_launch_pip_apply(const BlockList& QZ, const float* F, int c, int b,
-                                  const OutBlockList& Z, int64_t n, const int* cond,
-                                  const int* flags, uint64_t seed, int64_t row0,
-                                  hipStream_t stream);
 hipError_t n2v2r_launch_fill_normal(float* blk, int w, int64_t n, uint64_t seed, const int* flags,
                                     const int* cond, uint64_t ctr0, hipStream_t stream);
 hipError_t n2v2r_launch_resid(const BlockList& X, const BlockList& MX, const double* theta,
@@ -177,9 +158,6 @@ size_t n2v2r_rr_bt_scratch_bytes(int c);
 hipError_t n2v2r_launch_lds_poison(hipStream_t stream);
 hipError_t n2v2r_launch_nonfinite(const void* p, int64_t count, int f64, int* flag,
                                   hipStream_t stream);
-hipError_t n2v2r_launch_ts_tn_zsum(const BlockList& A, int64_t n, const float* const* parts,
-                                   int count, float* zout, double* partial, size_t partial_elems,
-                                   double* out, hipStream_t stream);
 hipError_t n2v2r_launch_pack_words(void* const* src, const int* dst_word, const int* words,
                                    const int* clear, int count, void* dst, hipStream_t stream);
 hipError_t n2v2r_launch_zsum(const float* const* parts, int count, float* zout, int64_t n,
@@ -211,10 +189,6 @@ inline bool rr_sturm_enabled() {
   const char* e = std::getenv("N2V2R_RR");
   return !(e && e[0] == 'b');
 }
-
-// Ritz vectors and images by one launch with the coefficients staged once per CU
-// (ritz_nn_kernel) where it applies (its A/B switch retired in round 5)
-inline bool ritz_nn_enabled() { return true; }
 
 // Lean images (banded Sturm Rayleigh-Ritz, one GPU) unless N2V2R_LEAN_W=0.  Read per fit.
 inline bool lean_enabled() {

@@ -136,7 +136,7 @@ extern "C" hipError_t n2v2r_launch_csr_rebase(const int64_t* ip, int64_t r0, int
 }
 
 // Row order of a partitioned layer's column share A[:, own rows] (layers.cpp ensure_colcsr) made
-// chunk-major for the pipelined reduce-scatter (solver.cpp apply_M_rs): global row j = g npad + i
+// chunk-major for the pipelined reduce-scatter (solver.cpp stage2_rs): global row j = g npad + i
 // (rank g's local row i, chunk c = i / rc of nch) moves to position
 // c W rc + g rows_c + (i - c rc), rows_c = min(rc, npad - c rc), so chunk c's W row blocks are one
 // contiguous range of the product -- what one reduce-scatter of that chunk sends.  Applied to the

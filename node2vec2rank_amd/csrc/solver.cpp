@@ -437,46 +437,141 @@ struct Eig {
       h->allreduce_f64(out, (size_t)A.count * A.width * B.count * B.width);
   }
 
-  // Partitioned CSR handles, reduce-scatter form (the default at W > 1):
-  // stage 1 as the gather form on the all-gathered X, then this rank's column share of stage 2,
-  // P = sum_k A_k[:, own rows] Z_k[own rows] over all (padded) global rows -- gathered from the
-  // rank's own Z rows only -- and ONE reduce-scatter of P into W's own rows: one all-gather + one
-  // reduce-scatter per application instead of K + 1 all-gathers.
-  void apply_M_rs(const float* xg, float* Wout) {
-    const int64_t ng = (int64_t)h->world * npad;
-    float* P = h->ews.zg.as<float>();  // the gather form's Z panels' buffer (>= ng x b)
-    double b0 = 0.0, b1 = 0.0;
-    for (int k = 0; k < K; ++k) b0 += layer_bytes(k, true);
+  // ---- W = M X: stage 1, Z_k = A_k^T X, and the forms of stage 2, W = sum_k A_k Z_k -------------
+
+  float* zk(int k) const { return h->ews.zk[k]->as<float>(); }
+  // partitioned handles: Z_k all-gathered from every rank (rank-major, global rows)
+  float* gathered_z(int k) const {
+    return h->ews.zg.as<float>() + (size_t)k * h->world * npad * b;
+  }
+  const float* stage2_in(int k) const { return h->comm ? gathered_z(k) : zk(k); }
+  // algorithmic bytes of one stage over all layers (fixed layer order)
+  double stage_bytes(bool transposed) const {
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += layer_bytes(k, transposed);
+    return s;
+  }
+
+  // Stage 1 of the CSR forms, one launch: Z_k = A_k^T xg for every layer, or for `layer` alone;
+  // the tiled column-block form when the fit uses it (col_blocks), else the flat one.
+  void stage1(const float* xg, int layer = -1) {
+    const int k0 = layer < 0 ? 0 : layer, nk = layer < 0 ? K : 1;
+    const double bytes = layer < 0 ? stage_bytes(true) : layer_bytes(layer, true);
     int te;
     if (col_blocks) {
       SpmmTileArgs a{};
-      a.blk = h->ews.tblk.as<CsrBlk>();
+      a.blk = h->ews.tblk.as<CsrBlk>() + (size_t)k0 * tile_nb;
       a.ldx = a.ldy = 8;
       a.n = n;
-      a.K = K;
+      a.K = nk;
       a.nb = tile_nb;
       a.sum = 0;
       a.tile_rows = tile_rows;
       a.wbits = tile_wb;
-      for (int k = 0; k < K; ++k) {
-        a.X[k] = xg;
-        a.Y[k] = h->ews.zk[k]->as<float>();
+      for (int i = 0; i < nk; ++i) {
+        a.X[i] = xg;
+        a.Y[i] = zk(k0 + i);
       }
       te = tbeg();
       HIPCHK(n2v2r_launch_spmm_tile(a, st));
     } else {
       SpmmArgs a{};
-      a.K = K;
+      a.K = nk;
       a.ldx = a.ldy = b;
-      for (int k = 0; k < K; ++k) {
-        a.A[k] = h->layers[k]->csr_t();
-        a.X[k] = xg;
-        a.Y[k] = h->ews.zk[k]->as<float>();
+      // split over the XCDs like the split stage 2 (24.2 -> 23.4 us at cfg2); one GPU only,
+      // where every launch takes all layers
+      a.split = split2 ? 1 : 0;
+      for (int i = 0; i < nk; ++i) {
+        a.A[i] = h->layers[k0 + i]->csr_t();
+        a.X[i] = xg;
+        a.Y[i] = zk(k0 + i);
       }
       te = tbeg();
       HIPCHK(n2v2r_launch_spmm(a, b, st));
     }
-    tend(te, 0, b0);
+    tend(te, 0, bytes);
+  }
+
+  // Stage 1 of the gather forms.  Partitioned: every Z_k all-gathered for stage 2 -- one launch
+  // per layer, each Z_k gathered on the collective stream while the next layer's stage 1 runs, or
+  // (N2V2R_GATHER_OVERLAP=0, K = 1) one launch and the gathers in line.
+  void stage1_gathered(const float* xg) {
+    if (h->comm && K > 1 && gather_overlap() && st == h->stream) {
+      for (int k = 0; k < K; ++k) {
+        stage1(xg, k);
+        h->gather_panel_async(zk(k), gathered_z(k), b, k);
+      }
+      for (int k = 0; k < K; ++k) h->gather_wait(k);
+      return;
+    }
+    stage1(xg);
+    if (h->comm)
+      for (int k = 0; k < K; ++k) h->gather_panel(zk(k), gathered_z(k), b);
+  }
+
+  // Stage 2, flat: one launch summing the layers into W -- or (split2) leaving per-layer partials
+  // on the layers' XCDs, W pending until the next Gram pass or materialize() sums them.
+  void stage2_flat(float* Wout) {
+    SpmmArgs s{};
+    s.K = K;
+    s.sum = 1;
+    s.ldx = s.ldy = b;
+    for (int k = 0; k < K; ++k) {
+      s.A[k] = h->layers[k]->csr();
+      s.X[k] = stage2_in(k);
+    }
+    s.Y[0] = Wout;
+    if (split2) {
+      materialize();  // (a previous image is always consumed by now; kept for safety)
+      s.sum = 0;
+      s.split = 1;
+      for (int k = 0; k < K; ++k) s.Y[k] = s2part(k);
+      pending = Wout;
+    }
+    const double bytes = stage_bytes(false);
+    const int te = tbeg();
+    HIPCHK(n2v2r_launch_spmm(s, b, st));
+    tend(te, 1, bytes);
+    for (int k = 0; k < K; ++k) {
+      const LayerDev& L = *h->layers[k];
+      algo_bytes += spmm_algo_bytes(L.nnz, L.unit, n, n, b) +
+                    spmm_algo_bytes(L.symmetric ? L.nnz : L.t_nnz,
+                                    L.symmetric ? L.unit : L.t_unit, n, n, b);
+    }
+    launches += 2;
+  }
+
+  // Stage 2, tiled column blocks: one launch over all layers
+  void stage2_tiled(float* Wout) {
+    SpmmTileArgs s{};
+    s.blk = h->ews.tblk.as<CsrBlk>() + (size_t)K * tile_nb;
+    s.ldx = s.ldy = 8;
+    s.n = n;
+    s.K = K;
+    s.nb = tile_nb;
+    s.sum = 1;
+    s.tile_rows = tile_rows;
+    s.wbits = tile_wb;
+    for (int k = 0; k < K; ++k) s.X[k] = stage2_in(k);
+    s.Y[0] = Wout;
+    const double b0 = stage_bytes(true), b1 = stage_bytes(false);
+    const int te = tbeg();
+    HIPCHK(n2v2r_launch_spmm_tile(s, st));
+    tend(te, 1, b1);
+    algo_bytes += b0 + b1;
+    launches += 2;
+  }
+
+  // Stage 2, reduce-scatter form (partitioned CSR handles, the default at W > 1, DESIGN section
+  // 6): after stage 1 on the all-gathered X, this rank's column share of stage 2,
+  // P = sum_k A_k[:, own rows] Z_k[own rows] over all (padded) global rows -- gathered from the
+  // rank's own Z rows only -- and ONE reduce-scatter of P into W's own rows: one all-gather + one
+  // reduce-scatter per application instead of K + 1 all-gathers.
+  void stage2_rs(float* Wout) {
+    const int64_t ng = (int64_t)h->world * npad;
+    float* P = h->ews.zg.as<float>();  // the gather form's Z panels' buffer (>= ng x b)
+    const double b0 = stage_bytes(true);
+    double b1 = 0.0;
     SpmmArgs s2{};
     s2.K = K;
     s2.sum = 1;
@@ -484,11 +579,11 @@ struct Eig {
     for (int k = 0; k < K; ++k) {
       const LayerDev& L = *h->layers[k];
       s2.A[k] = L.csr_c();
-      s2.X[k] = h->ews.zk[k]->as<float>();
+      s2.X[k] = zk(k);
       b1 += spmm_algo_bytes(L.c_nnz, s2.A[k].unit != 0, ng, npad, b);
     }
     s2.Y[0] = P;
-    te = tbeg();
+    const int te = tbeg();
     if (rs_chunks <= 1) {
       HIPCHK(n2v2r_launch_spmm(s2, b, st));
       tend(te, 1, b1);
@@ -522,11 +617,35 @@ struct Eig {
     launches += 2;
   }
 
+  // Dense layers, both stages: Z_k = A_k^T X, W = sum_k A_k Z_k (fixed layer order), GEMMs on
+  // the local rows
+  void apply_M_dense(const float* xg, float* Wout) {
+    const int64_t ng = (int64_t)h->world * npad;  // rows of a gathered panel
+    // per GEMM launch: the layer rows read once (4 n N) + the panel read and the output rows
+    const double gb = 4.0 * (double)n * (double)h->n + 4.0 * (double)(ng + n) * b;
+    for (int k = 0; k < K; ++k) {
+      const LayerDev& L = *h->layers[k];
+      const int te = tbeg();
+      h->dense_apply(L.dense_at(), L.lda, xg, b, b, zk(k), b, 0.f, nullptr,
+                     h->comm ? nullptr : L.dense_a());
+      tend(te, 0, gb);
+    }
+    for (int k = 0; k < K; ++k) {
+      const LayerDev& L = *h->layers[k];
+      if (h->comm) h->gather_panel(zk(k), gathered_z(k), b);
+      const int te = tbeg();
+      h->dense_apply(L.dense_a(), L.lda, stage2_in(k), b, b, Wout, b, k == 0 ? 0.f : 1.f, nullptr,
+                     h->comm ? nullptr : L.dense_at());
+      tend(te, 1, gb);
+      algo_bytes += 2.0 * gb;
+    }
+    launches += 2 * K;
+  }
+
   // W = M X = sum_k A_k (A_k^T X); X, W local, gathered panels for the column side
   void apply_M(const float* X, float* Wout) {
     const double t0 = now_ms();
     lds_poison();
-    const int64_t ng = (int64_t)h->world * npad;  // rows of a gathered panel
     const float* xg = X;
     if (h->comm) {
       float* xgb = h->gath.as<float>();
@@ -534,199 +653,83 @@ struct Eig {
       xg = xgb;
     }
     if (h->dense_layers()) {
-      // Z_k = A_k^T X, W = sum_k A_k Z_k (fixed layer order), dense GEMMs on the local rows
-      // per GEMM launch: the layer rows read once (4 n N) + the panel read and the output rows
-      const double gb = 4.0 * (double)n * (double)h->n + 4.0 * (double)(ng + n) * b;
-      for (int k = 0; k < K; ++k) {
-        const LayerDev& L = *h->layers[k];
-        const int te = tbeg();
-        h->dense_apply(L.dense_at(), L.lda, xg, b, b, h->ews.zk[k]->as<float>(), b, 0.f, nullptr,
-                       h->comm ? nullptr : L.dense_a());
-        tend(te, 0, gb);
-      }
-      for (int k = 0; k < K; ++k) {
-        const LayerDev& L = *h->layers[k];
-        const float* zin = h->ews.zk[k]->as<float>();
-        if (h->comm) {
-          float* zgk = h->ews.zg.as<float>() + (size_t)k * ng * b;
-          h->gather_panel(h->ews.zk[k]->as<float>(), zgk, b);
-          zin = zgk;
-        }
-        const int te = tbeg();
-        h->dense_apply(L.dense_a(), L.lda, zin, b, b, Wout, b, k == 0 ? 0.f : 1.f, nullptr,
-                       h->comm ? nullptr : L.dense_at());
-        tend(te, 1, gb);
-        algo_bytes += 2.0 * gb;
-      }
-      launches += 2 * K;
-      t_spmm += now_ms() - t0;
-      return;
-    }
-    if (rs_form) {
-      apply_M_rs(xg, Wout);
-      t_spmm += now_ms() - t0;
-      return;
-    }
-    if (col_blocks) {
-      apply_M_tiled(xg, Wout, ng);
-      t_spmm += now_ms() - t0;
-      return;
-    }
-    SpmmArgs a{};
-    a.K = K;
-    a.sum = 0;
-    a.ldx = b;
-    a.ldy = b;
-    a.colscale = nullptr;
-    a.split = split2 ? 1 : 0;  // first stage split over the XCDs too (24.2 -> 23.4 us at cfg2)
-    for (int k = 0; k < K; ++k) {
-      a.A[k] = h->layers[k]->csr_t();
-      a.X[k] = xg;
-      a.Y[k] = h->ews.zk[k]->as<float>();
-    }
-    double sb0 = 0.0, sb1 = 0.0;
-    for (int k = 0; k < K; ++k) {
-      sb0 += layer_bytes(k, true);
-      sb1 += layer_bytes(k, false);
-    }
-    // partitioned: stage 1 one layer per launch, each layer's Z_k all-gathered on the
-    // collective stream while the next layer's stage 1 runs (N2V2R_GATHER_OVERLAP=0: in line)
-    const bool ovl = h->comm && K > 1 && gather_overlap() && st == h->stream;
-    int te = -1;
-    if (ovl) {
-      for (int k = 0; k < K; ++k) {
-        SpmmArgs a1 = a;
-        a1.K = 1;
-        a1.split = 0;
-        a1.A[0] = a.A[k];
-        a1.X[0] = xg;
-        a1.Y[0] = a.Y[k];
-        te = tbeg();
-        HIPCHK(n2v2r_launch_spmm(a1, b, st));
-        tend(te, 0, layer_bytes(k, true));
-        h->gather_panel_async(h->ews.zk[k]->as<float>(),
-                              h->ews.zg.as<float>() + (size_t)k * ng * b, b, k);
-      }
-      for (int k = 0; k < K; ++k) h->gather_wait(k);
+      apply_M_dense(xg, Wout);
+    } else if (rs_form) {
+      stage1(xg);
+      stage2_rs(Wout);
     } else {
-      te = tbeg();
-      HIPCHK(n2v2r_launch_spmm(a, b, st));
-      tend(te, 0, sb0);
+      stage1_gathered(xg);
+      if (col_blocks)
+        stage2_tiled(Wout);
+      else
+        stage2_flat(Wout);
     }
-    SpmmArgs s{};
-    s.K = K;
-    s.sum = 1;
-    s.ldx = b;
-    s.ldy = b;
-    s.colscale = nullptr;
-    for (int k = 0; k < K; ++k) {
-      s.A[k] = h->layers[k]->csr();
-      if (h->comm) {
-        float* zgk = h->ews.zg.as<float>() + (size_t)k * ng * b;
-        if (!ovl) h->gather_panel(h->ews.zk[k]->as<float>(), zgk, b);
-        s.X[k] = zgk;
-      } else {
-        s.X[k] = h->ews.zk[k]->as<float>();
-      }
-    }
-    s.Y[0] = Wout;
-    if (split2) {
-      materialize();  // (a previous image is always consumed by now; kept for safety)
-      s.sum = 0;
-      s.split = 1;
-      for (int k = 0; k < K; ++k) s.Y[k] = s2part(k);
-      pending = Wout;
-    }
-    te = tbeg();
-    HIPCHK(n2v2r_launch_spmm(s, b, st));
-    tend(te, 1, sb1);
-    for (int k = 0; k < K; ++k) {
-      const LayerDev& L = *h->layers[k];
-      algo_bytes += spmm_algo_bytes(L.nnz, L.unit, n, n, b) +
-                    spmm_algo_bytes(L.symmetric ? L.nnz : L.t_nnz,
-                                    L.symmetric ? L.unit : L.t_unit, n, n, b);
-    }
-    launches += 2;
     t_spmm += now_ms() - t0;
   }
 
-  // apply_M with the tiled column-block SpMM: one launch per stage over all layers
-  void apply_M_tiled(const float* xg, float* Wout, int64_t ng) {
-    const CsrBlk* tb = h->ews.tblk.as<CsrBlk>();
-    SpmmTileArgs a{};
-    a.blk = tb;
-    a.ldx = a.ldy = 8;
-    a.n = n;
-    a.K = K;
-    a.nb = tile_nb;
-    a.sum = 0;
-    a.tile_rows = tile_rows;
-    a.wbits = tile_wb;
-    double b0 = 0.0, b1 = 0.0;
-    for (int k = 0; k < K; ++k) {
-      a.X[k] = xg;
-      a.Y[k] = h->ews.zk[k]->as<float>();
-      b0 += layer_bytes(k, true);
-      b1 += layer_bytes(k, false);
-    }
-    // partitioned: one launch per layer, Z_k gathered while layer k + 1 runs (as apply_M)
-    const bool ovl = h->comm && K > 1 && gather_overlap() && st == h->stream;
-    int te = -1;
-    if (ovl) {
-      for (int k = 0; k < K; ++k) {
-        SpmmTileArgs a1 = a;
-        a1.K = 1;
-        a1.blk = tb + (size_t)k * tile_nb;
-        a1.X[0] = xg;
-        a1.Y[0] = a.Y[k];
-        te = tbeg();
-        HIPCHK(n2v2r_launch_spmm_tile(a1, st));
-        tend(te, 0, layer_bytes(k, true));
-        h->gather_panel_async(h->ews.zk[k]->as<float>(),
-                              h->ews.zg.as<float>() + (size_t)k * ng * b, b, k);
-      }
-      for (int k = 0; k < K; ++k) h->gather_wait(k);
-    } else {
-      te = tbeg();
-      HIPCHK(n2v2r_launch_spmm_tile(a, st));
-      tend(te, 0, b0);
-    }
-    SpmmTileArgs s2 = a;
-    s2.blk = tb + (size_t)K * tile_nb;
-    s2.sum = 1;
-    for (int k = 0; k < K; ++k) {
-      s2.X[k] = h->ews.zk[k]->as<float>();
-      if (h->comm) {
-        float* zgk = h->ews.zg.as<float>() + (size_t)k * ng * b;
-        if (!ovl) h->gather_panel(h->ews.zk[k]->as<float>(), zgk, b);
-        s2.X[k] = zgk;
-      }
-      s2.Y[k] = nullptr;
-    }
-    s2.Y[0] = Wout;
-    te = tbeg();
-    HIPCHK(n2v2r_launch_spmm_tile(s2, st));
-    tend(te, 1, b1);
-    algo_bytes += b0 + b1;
-    launches += 2;
+  // ---- the orthogonalisation passes --------------------------------------------------------------
+  // Three kinds of pass, each with a flag slot s of its own: refill flags at
+  // flg_p + 64 s, any-flag at any_p + s.  any_p + 3 is the cycle's sticky flag.
+
+  // the refill seed of the next pass: one per pass, in launch order
+  uint64_t next_fill_seed() { return seed ^ (0xABCDull + ++fill_counter); }
+
+  PipPass pass_in_slot(int s) const {
+    PipPass p;
+    p.flags = flg_p + 64 * s;
+    p.any_flag = any_p + s;
+    p.row0 = row0;
+    return p;
+  }
+  // The blocks a block's first pass takes: `local` (the blocks W_from couples to in exact
+  // arithmetic), or the whole basis when there is no such subset or full_first asks for it.
+  const std::vector<float*>& first_blocks(const std::vector<float*>& basis,
+                                          const std::vector<float*>* local) const {
+    return local && !full_first && local->size() < basis.size() ? *local : basis;
+  }
+  // First pass (slot 0) against `first` = first_blocks(basis, local).  save (band Rayleigh-Ritz):
+  // the Gram rows of the `local` blocks, the last ones of `first`, are kept as a band column.
+  PipPass first_pass(const std::vector<float*>& first, const std::vector<float*>* local,
+                     double* save, int* sticky, double* rsave) const {
+    const int nsave = (save && local) ? (int)local->size() : 0;
+    PipPass p = pass_in_slot(0);
+    p.first = 1;
+    p.save = nsave ? save : nullptr;
+    p.save_row0 = ((int)first.size() - nsave) * b;
+    p.save_rows = nsave * b;
+    p.sticky = sticky;
+    p.rsave = rsave;
+    return p;
+  }
+  // Selective full pass (slot 1): blocks whose coupling to Z is within reorth_tol are left out
+  PipPass selective_pass(int* sticky, double* rsave = nullptr) const {
+    PipPass p = pass_in_slot(1);
+    p.skip_tol = reorth_tol;
+    p.skipped = reorth_tol != 0.f ? h->ews.skipc.as<int>() : nullptr;
+    p.sticky = sticky;
+    p.rsave = rsave;
+    return p;
+  }
+  // Third pass (slot 2): runs only when the selective pass had to refill a column
+  PipPass third_pass() const {
+    PipPass p = pass_in_slot(2);
+    p.cond = any_p + 1;
+    return p;
   }
 
   // One fused BCGS + CholQR pass: G = [Q Z]^T Z -> R^{-1} -> Z <- [Q Z] [-C R^{-1}; R^{-1}],
-  // refill deficient columns.  `cond` (device int, nullptr = always) skips the pass when zero.
-  void pip_pass(float* Z, const std::vector<float*>& basis, const int* cond, int* flags_out,
-                int* any_out, const float* Zin = nullptr, double* save = nullptr,
-                int save_row0 = 0, int save_rows = 0, int* sticky = nullptr,
-                double* rsave = nullptr, float skip_tol = 0.f, bool first = false) {
-    // first: the block's first pass (a pivot the Pythagorean Gram cannot resolve is clamped and
-    // the column kept); later passes refill such columns (dense.hip, PIP_CANCEL)
-    // Zin (default Z): the block to orthogonalise; the result is written to Z
+  // refill deficient columns.  Takes the next refill seed.
+  // Zin (default Z): the block to orthogonalise; the result is written to Z
+  void pip_pass(float* Z, const std::vector<float*>& basis, PipPass p,
+                const float* Zin = nullptr) {
+    p.seed = next_fill_seed();
     const float* zin = Zin ? Zin : Z;
     const int nq = (int)basis.size();
     std::vector<float*> qz(basis);
     qz.push_back(const_cast<float*>(zin));
     const BlockList L = blocks(qz, 0, nq + 1);
     bool done = false;
-    if (pending && zin == pending && !cond && !h->comm) {
+    if (pending && zin == pending && !p.cond && !h->comm) {
       // the Gram pass that first reads the pending image also stores it
       const float* parts[8];
       for (int k = 0; k < K; ++k) parts[k] = s2part(k);
@@ -741,25 +744,20 @@ struct Eig {
     }
     if (!done) {
       if (zin == pending) materialize();
-      tn(L, one(zin), gsm_p, cond);
+      tn(L, one(zin), gsm_p, p.cond);
     }
-    if (b == 8 && nq * b <= N2V2R_BAND_MAXC && pip_fused()) {
+    if (b == 8 && nq * b <= N2V2R_BAND_MAXC) {
       // b = 8: the Cholesky step runs inside the apply launch (every workgroup factors G)
-      HIPCHK(n2v2r_launch_pip_fused(blocks(qz, 0, nq), zin, Z, gsm_p, nq * b,
-                                    n, cond, flags_out, any_out, save, save_row0, save_rows,
-                                    sticky, seed ^ (0xABCDull + ++fill_counter), row0, rsave,
-                                    skip_tol, skip_tol != 0.f ? h->ews.skipc.as<int>() : nullptr,
-                                    first ? 1 : 0, st));
+      HIPCHK(n2v2r_launch_pip_fused(blocks(qz, 0, nq), zin, Z, gsm_p, nq * b, n, p, st));
       return;
     }
-    if (rsave && b != 8) throw StatusFail{N2V2R_ERR_INTERNAL, "R output needs b = 8"};
+    // wider blocks: the two-launch form
+    if (p.rsave && b != 8) throw StatusFail{N2V2R_ERR_INTERNAL, "R output needs b = 8"};
     // (skip_tol: the unfused pass always applies)
     HIPCHK(n2v2r_launch_pip_chol(gsm_p, nq * b, b, h->ews.rinv.as<double>(),
-                                 flags_out, any_out, cond, save, save_row0, save_rows,
-                                 h->ews.fcoef.as<float>(), sticky, rsave, first ? 1 : 0, st));
-    // rank-deficient columns (flags_out) are refilled with random values by the same launch
-    HIPCHK(n2v2r_launch_pip_apply(L, h->ews.fcoef.as<float>(), nq * b, b, out_one(Z), n, cond,
-                                  flags_out, seed ^ (0xABCDull + ++fill_counter), row0, st));
+                                 h->ews.fcoef.as<float>(), p, st));
+    // rank-deficient columns (p.flags) are refilled with random values by the same launch
+    HIPCHK(n2v2r_launch_pip_apply(L, h->ews.fcoef.as<float>(), nq * b, b, out_one(Z), n, p, st));
   }
 
   // orthonormalise Zin (default: Z in place) against `basis` and within itself into Z.
@@ -780,15 +778,11 @@ struct Eig {
     const double t0 = now_ms();
     lds_poison();
     int* flg = flg_p;
-    int* any = any_p;
-    const bool loc = local && !full_first && local->size() < basis.size();
-    const std::vector<float*>& first = loc ? *local : basis;
-    const int nsave = (save && local) ? (int)local->size() : 0;
+    const std::vector<float*>& first = first_blocks(basis, local);
     // (no sticky flag here: a column the first pass cancelled -- scaled, not normalised -- is
     // normalised by the full pass that always follows; a refill there (a later pass) sets it.
     // BASELINE cfg3's first images cancel: with the flag each fit expanded cycle 0 twice)
-    pip_pass(Z, first, nullptr, flg, any, Zin, nsave ? save : nullptr,
-             ((int)first.size() - nsave) * b, nsave * b, nullptr, rsave_first, 0.f, true);
+    pip_pass(Z, first, first_pass(first, local, save, nullptr, rsave_first), Zin);
     if (debug_ortho()) {  // pass 1's Gram [Q Z]^T Z (still in gsm_p)
       const int c1 = (int)first.size() * b;
       std::vector<double> g((size_t)(c1 + b) * b);
@@ -806,11 +800,11 @@ struct Eig {
     }
     dbg_ortho(Z, first, "after pass 1 (local)", flg);
     // (rsave_first: the second pass's R too, folded into the first's: R2 R1)
-    pip_pass(Z, basis, nullptr, flg + 64, any + 1, nullptr, nullptr, 0, 0,
-             lazy ? any + 3 : nullptr, rsave_first ? rsave_first + 64 : nullptr, reorth_tol);
+    pip_pass(Z, basis, selective_pass(lazy ? any_p + 3 : nullptr,
+                                      rsave_first ? rsave_first + 64 : nullptr));
     if (rsave_first) HIPCHK(n2v2r_launch_rmul8(rsave_first + 64, rsave_first, st));
     dbg_ortho(Z, basis, "after pass 2 (full, selective)", flg + 64);
-    if (!lazy) pip_pass(Z, basis, any + 1, flg + 128, any + 2);
+    if (!lazy) pip_pass(Z, basis, third_pass());
     if (!lazy) dbg_ortho(Z, basis, "after pass 3", flg + 128);
     t_ortho += now_ms() - t0;
   }
@@ -822,9 +816,7 @@ struct Eig {
     if (it == basis.end()) throw StatusFail{N2V2R_ERR_INTERNAL, "deferred block left the basis"};
     const std::vector<float*> pre(basis.begin(), it);
     const double t0 = now_ms();
-    if (!pre.empty())
-      pip_pass(deferred, pre, nullptr, flg_p + 64, any_p + 1, nullptr, nullptr, 0, 0, any_p + 3,
-               nullptr, reorth_tol);
+    if (!pre.empty()) pip_pass(deferred, pre, selective_pass(any_p + 3));
     t_ortho += now_ms() - t0;
     deferred = nullptr;
   }
@@ -853,17 +845,18 @@ struct Eig {
     if (e == hipErrorNotSupported) return false;
     if (e != hipSuccess) throw HipFail{e, "n2v2r_launch_ts_tn2"};
     if (h->comm) h->allreduce_f64(g2, 2 * (size_t)(nq_old + 2) * 64);
+    // Za's selective pass (its R kept for the fix-up), then Zb's; each with its refill seed
     double* ra = h->ews.pair_ra.as<double>();
-    int* skc = reorth_tol != 0.f ? h->ews.skipc.as<int>() : nullptr;
+    PipPass pa = selective_pass(any_p + 3, ra), pz = selective_pass(any_p + 3);
+    pa.seed = next_fill_seed();
+    pz.seed = next_fill_seed();
     if (pair_apply) {
-      // both selective passes in one read of the basis (the seeds the two launches below take)
-      const uint64_t sa = seed ^ (0xABCDull + (fill_counter + 1));
-      const uint64_t sb = seed ^ (0xABCDull + (fill_counter + 2));
+      // both in one read of the basis
       const hipError_t pe = n2v2r_launch_pip_pair(
-          blocks(basis, 0, nq_old), deferred, zb, g2, n, flg_p + 64, any_p + 1, any_p + 3, sa, sb,
-          row0, reorth_tol, skc, h->ews.pair_plan.as<int>(), h->ews.pair_plan.bytes, st);
+          blocks(basis, 0, nq_old), deferred, zb, g2, n, pa.flags, pa.any_flag, pa.sticky, pa.seed,
+          pz.seed, row0, reorth_tol, pa.skipped, h->ews.pair_plan.as<int>(),
+          h->ews.pair_plan.bytes, st);
       if (pe == hipSuccess) {
-        fill_counter += 2;
         t_ortho += now_ms() - t0;
         deferred = nullptr;
         return true;
@@ -871,15 +864,10 @@ struct Eig {
       if (pe != hipErrorNotSupported) throw HipFail{pe, "n2v2r_launch_pip_pair"};
     }
     HIPCHK(n2v2r_launch_pip_fused(blocks(basis, 0, nq_old), deferred, deferred, g2, nq_old * b, n,
-                                  nullptr, flg_p + 64, any_p + 1, nullptr, 0, 0, any_p + 3,
-                                  seed ^ (0xABCDull + ++fill_counter), row0, ra, reorth_tol, skc,
-                                  0, st));
+                                  pa, st));
     HIPCHK(n2v2r_launch_pair_fixup(g2, nq_old + 2, nq_old, ra, st));
     HIPCHK(n2v2r_launch_pip_fused(blocks(basis, 0, nq_old + 1), zb, zb,
-                                  g2 + (size_t)(nq_old + 2) * 64, (nq_old + 1) * b, n, nullptr,
-                                  flg_p + 64, any_p + 1, nullptr, 0, 0, any_p + 3,
-                                  seed ^ (0xABCDull + ++fill_counter), row0, nullptr, reorth_tol,
-                                  skc, 0, st));
+                                  g2 + (size_t)(nq_old + 2) * 64, (nq_old + 1) * b, n, pz, st));
     t_ortho += now_ms() - t0;
     deferred = nullptr;
     return true;
@@ -915,21 +903,17 @@ struct Eig {
       // waiting block and this one get their full passes
       const double t0 = now_ms();
       lds_poison();
-      const bool lp = loc.size() < basis.size();
-      const std::vector<float*>& first = lp ? loc : basis;
-      const int nsave = save ? (int)loc.size() : 0;
+      const std::vector<float*>& first = first_blocks(basis, &loc);
       // a refill or heavy cancellation here sets the sticky flag: the block may not go to its
       // SpMM before its full pass, so the cycle is expanded again without deferral
-      pip_pass(z, first, nullptr, flg_p, any_p, w_from, nsave ? save : nullptr,
-               ((int)first.size() - nsave) * b, nsave * b, any_p + 3, nullptr, 0.f, true);
+      pip_pass(z, first, first_pass(first, &loc, save, any_p + 3, nullptr), w_from);
       t_ortho += now_ms() - t0;
       if (deferred && pair_pass(z, basis)) {
         // (both full passes done)
       } else if (deferred) {
         flush_deferred(basis);
         const double t1 = now_ms();
-        pip_pass(z, basis, nullptr, flg_p + 64, any_p + 1, nullptr, nullptr, 0, 0, any_p + 3,
-                 nullptr, reorth_tol);
+        pip_pass(z, basis, selective_pass(any_p + 3));
         t_ortho += now_ms() - t1;
       } else {
         deferred = z;
@@ -1083,7 +1067,7 @@ struct Eig {
     // Lean images on a partitioned handle too: every quantity they read back (R of the restart
     // projection, the Ritz values and coefficients, the true residuals) is all-reduced first,
     // so every rank takes the same decisions.
-    lean = b == 8 && pip_fused() && band_rr && sturm && !lean_off && lean_enabled();
+    lean = b == 8 && band_rr && sturm && !lean_off && lean_enabled();
     h->ews.skipc.ensure(sizeof(int) * (4 + N2V2R_BAND_MAXC / 8));  // [0]: skipped, [1 + blk]
     HIPCHK(hipMemsetAsync(h->ews.skipc.p, 0, sizeof(int) * (4 + N2V2R_BAND_MAXC / 8), st));
     // R of the restart block's two passes
@@ -1111,7 +1095,7 @@ struct Eig {
     const char* e = std::getenv("N2V2R_REORTH_DEFER");  // read per fit (A/B runs)
     // lean images only: with every image kept, the Rayleigh-Ritz and the residuals read the
     // images themselves, and a deferred block's image is the uncorrected block's
-    defer = !(e && e[0] == '0') && b == 8 && pip_fused() && lean;
+    defer = !(e && e[0] == '0') && lean;
     deferred = nullptr;
     // a pair's two selective passes: fused (planned by one small launch, applied in one read
     // of the basis) from 2^19 rows on, where the second read of the basis costs more than the
@@ -1228,8 +1212,8 @@ struct Eig {
     lds_poison();
     const int per_launch = std::max(1, 128 / b);  // output blocks per ts_nn launch (<= 128 cols)
     bool ritz_done = false;
-    if (b == 8 && keep <= 96 && ritz_nn_enabled()) {
-      // both products in one launch, the coefficients staged once per CU
+    if (b == 8 && keep <= 96) {
+      // both products in one launch (ritz_nn_kernel), the coefficients staged once per CU
       OutBlockList ox{}, omx{};
       ox.width = omx.width = b;
       ox.count = omx.count = pb;
@@ -1256,10 +1240,10 @@ struct Eig {
       // G slice: columns [q0b*b, q0b*b + nt*b) of S (ld = keep)
       const float* g = h->ews.csmall.as<float>() + q0b * b;
       HIPCHK(n2v2r_launch_ts_nn(blocks(Q, 0, nq), g, keep, nt * b, ox, one(nullptr), 1.f, 0.f, n,
-                                nullptr, nullptr, 0, st));
+                                st));
       if (!lean)
         HIPCHK(n2v2r_launch_ts_nn(blocks(W, 0, nq), g, keep, nt * b, omx, one(nullptr), 1.f, 0.f,
-                                  n, nullptr, nullptr, 0, st));
+                                  n, st));
     }
     for (int q = 0; q < pb; ++q) {
       dbg(X[q], n * b, false, "Ritz vectors X = Q S");

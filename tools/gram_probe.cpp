@@ -15,15 +15,7 @@
 #include <random>
 #include <vector>
 
-#include "common.h"
-
-extern "C" hipError_t n2v2r_launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n,
-                                         double* partial, size_t partial_elems, double* out,
-                                         const int* cond, hipStream_t stream);
-extern "C" hipError_t n2v2r_launch_ts_tn_zsum(const BlockList& A, int64_t n,
-                                              const float* const* parts, int count, float* zout,
-                                              double* partial, size_t partial_elems, double* out,
-                                              hipStream_t stream);
+#include "pip_pass.h"
 
 #define CK(x)                                                                  \
   do {                                                                         \
