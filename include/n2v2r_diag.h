@@ -38,6 +38,25 @@ int n2v2r_spmm_col_blocks(const n2v2r_handle* h, int b);
  * row-major fp32 eigenvectors (the Ritz coefficients UASE consumes). */
 int n2v2r_rr_top(n2v2r_handle* h, int c, const double* H, int p, double* w, float* S);
 
+/* One orthogonalisation pass at block width 8 alone (tests), through the solver's own launchers,
+ * on a one-GPU handle.  Q: nq >= 1 basis blocks of n x 8 fp32, one after the other; Za (and Zb):
+ * n x 8 fp32, orthogonalised in place.  tau: the selective threshold (PipPass skip_tol; 0: every
+ * block); seed: of the refill deviates.
+ *   Zb == NULL: the Gram [Q Za]^T Za and one fused pass of Za against Q; first: the pass is the
+ *     block's first (a pivot the Gram cannot resolve is clamped and the column kept).
+ *     gram: (nq + 1) x 8 x 8 fp64; R: the pass's R (8 x 8 fp64, the identity for a skipped pass).
+ *   Zb != NULL (first must be 0): the solver's paired full pass, Za against Q and Zb against
+ *     [Q Za'] from the two-block Gram, as three launches (form 0) or through the paired apply
+ *     (form 1); Zb's pass draws with seed + 1.  gram: 2 x (nq + 2) x 8 x 8 fp64 (Za's Gram, then
+ *     Zb's with its rows against Za rewritten against the corrected Za').  R is not written.
+ * flags[8], any_flag: as the last pass left them.  skipped: nq + 1 (nq + 2) counters, [0] the
+ * passes skipped whole, [1 + k] the times block k was applied (all zero when tau == 0).
+ * N2V2R_ERR_BAD_ARG where a launcher refuses the shape (a basis past 768 columns, a plan that
+ * does not fit with form 1) and on a partitioned or multi-GPU handle. */
+int n2v2r_pip_pass(n2v2r_handle* h, int64_t n, int nq, const float* Q, float* Za, float* Zb,
+                   float tau, int first, int form, uint64_t seed, double* gram, double* R,
+                   int* flags, int* any_flag, int* skipped);
+
 /* Banded Rayleigh-Ritz stage alone (tests; block width 8, c <= 512, kp + 8 <= 192): the
  * projected matrix of a Krylov-Schur cycle given as UASE keeps it.  Basis order [X (kp
  * columns, diagonal theta_prev), E, Z_2, ...] in 8-wide blocks; hband holds band column

@@ -52,7 +52,7 @@ EXPORTED = [
     "n2v2r_rr_top", "n2v2r_rr_band_top", "n2v2r_set_layer_dense", "n2v2r_project",
     "n2v2r_create_multi", "n2v2r_multi_devices", "n2v2r_h2d_layer_bytes",
     "n2v2r_set_layer_corr", "n2v2r_get_layer_dense", "n2v2r_transform_layer",
-    "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles",
+    "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles", "n2v2r_pip_pass",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -159,6 +159,9 @@ def load(path: str | None = None):
                                             ctypes.POINTER(ctypes.c_double)]),
             "n2v2r_spmm_col_blocks": (_i, [_vp, _i]),
             "n2v2r_rr_top": (_i, [_vp, _i, _p(np.float64), _i, _p(np.float64), _p(np.float32)]),
+            "n2v2r_pip_pass": (_i, [_vp, _i64, _i, _p(np.float32), _p(np.float32), _vp,
+                                    ctypes.c_float, _i, _i, ctypes.c_uint64, _p(np.float64), _vp,
+                                    _p(np.int32), _p(np.int32), _p(np.int32)]),
             "n2v2r_rr_band_top": (_i, [_vp, _i, _i, _p(np.float64), ctypes.c_int64, _vp, _i,
                                        _p(np.float64), _p(np.float32)]),
             "n2v2r_set_layer_dense": (_i, [_vp, _i, _i64, _p(np.float32), _i]),
@@ -700,6 +703,33 @@ class Engine:
         S = np.empty((c, p), dtype=np.float32)
         self._check(self.lib.n2v2r_rr_top(self.h, c, H, int(p), w, S), "rr_top")
         return w, S
+
+    def pip_pass(self, Q, Za, Zb=None, tau: float = 0.0, first: int = 0, form: int = 0,
+                 seed: int = 1):
+        """One orthogonalisation pass at block width 8 alone (see n2v2r_pip_pass).  Q: (nq, n, 8)
+        fp32; Za, Zb: (n, 8) fp32 (Zb given: the paired full pass, form 0 its three launches,
+        form 1 the paired apply).  Returns a dict: the block(s) after the pass, the fp64 Gram the
+        pass used ((nq + 1, 8, 8), or (2, nq + 2, 8, 8)), R (single pass), flags, any_flag and
+        the skip counters."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        nq, n = Q.shape[0], Q.shape[1]
+        za = np.array(Za, dtype=np.float32, order="C")
+        zb = None if Zb is None else np.array(Zb, dtype=np.float32, order="C")
+        if Q.shape != (nq, n, 8) or za.shape != (n, 8) or (zb is not None and zb.shape != (n, 8)):
+            raise ValueError("pip_pass: Q is (nq, n, 8), Za and Zb are (n, 8)")
+        nz = 1 if zb is None else 2
+        gram = np.empty((nq + 1, 8, 8) if zb is None else (2, nq + 2, 8, 8), dtype=np.float64)
+        R = np.empty((8, 8), dtype=np.float64) if zb is None else None
+        flags = np.empty(8, dtype=np.int32)
+        any_flag = np.empty(1, dtype=np.int32)
+        skipped = np.empty(nq + nz, dtype=np.int32)
+        self._check(self.lib.n2v2r_pip_pass(
+            self.h, n, nq, Q, za, None if zb is None else zb.ctypes.data_as(ctypes.c_void_p),
+            float(tau), int(first), int(form), int(seed), gram,
+            None if R is None else R.ctypes.data_as(ctypes.c_void_p), flags, any_flag, skipped),
+            "pip_pass")
+        return {"Za": za, "Zb": zb, "gram": gram, "R": R, "flags": flags,
+                "any_flag": int(any_flag[0]), "skipped": skipped}
 
     def rr_band_top(self, hband, c: int, kp: int, theta_prev, p: int):
         """Banded Rayleigh-Ritz stage alone (see n2v2r_rr_band_top).  Returns (w, S)."""

@@ -1,20 +1,23 @@
 // Tall-skinny dense kernels for the block Krylov-Schur eigensolver (gfx950, wave64).
 //
-// Basis storage: blocks of N x W fp32 (W = 32 or 64), row-major, one allocation per block.
-// Every product is cut into 32 x 32 MFMA tiles of v_mfma_f32_32x32x2_f32 (exact fp32
-// products, fp32 accumulate; C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) +
-// 4 (lane >> 5)).
-//   ts_tn : G = A^T B   (ca x cb, reduction over N rows).  Per workgroup a chunk of rows;
-//           4 waves split the chunk, their fp32 tiles are summed in fp64 through LDS and
-//           written as a per-chunk fp64 partial; a second kernel sums the chunks in fixed
-//           order (deterministic, no atomics).
-//   ts_nn : O = alpha A G + beta C   (N x cb).  One wave per 32 output rows and ALL of the
+// Basis storage: blocks of N x W fp32, row-major, one allocation per block.  The solver runs at
+// W = 8; the general-width kernels (W = 16 .. 64) remain for the wider products.
+//   ts_tn : G = A^T B (reduction over the N rows) as per-chunk fp64 partials that a second
+//           kernel sums in fixed order (deterministic, no atomics).  At W = 8 the streaming
+//           forms: one wave per (basis block, row chunk), fp32 products of at most 256 rows
+//           per lane, an fp64 reduce-scatter over the row lanes (tn_fma, tn_fold_store); one
+//           right-hand side with Z staged through LDS, Z summed from its per-layer parts on
+//           the way (ts_tn_zsum_kernel), or two right-hand sides in one read of the basis
+//           (ts_tn_stream2_kernel).  Wider blocks: 32 x 32 tiles of v_mfma_f32_32x32x2_f32.
+//   ts_nn : O = alpha A G + beta C (N x cb).  One wave per 32 output rows and ALL of the
 //           output columns (so O may alias A or C: each wave reads only its own rows).
-//           A rows are read as 16-B loads; the k order inside each 8-column group is
-//           permuted consistently for A and G (lane half h carries columns 4h..4h+3).
-//   chol_inv : one-workgroup fp64 Cholesky G = R^T R (+shift on breakdown) and R^{-1},
-//           flagging rank-deficient columns; rows of those columns are refilled with
-//           random values by fill_flagged so the next CGS pass can orthogonalise them.
+//   pip   : one BCGS-PIP orthogonalisation pass Z <- (Z - Q C) R^{-1} from the Gram
+//           G = [Q Z]^T Z.  At W = 8 one launch (pip_fused_kernel), or one launch for the two
+//           passes of a pair (pair_plan_kernel + pip_pair_kernel); both are built from one
+//           prologue (pip_select, pip_factor: which blocks the pass applies, P = Z^T Z - C^T C,
+//           its Cholesky factor under the PIP_CANCEL rule below) and one row stream
+//           (pip_row_map .. pip_finish; flagged columns are refilled with counter deviates).
+//           Wider blocks: pip_chol_kernel, then the apply as a ts_nn product.
 #include "common.h"
 #include "pip_pass.h"
 
@@ -464,14 +467,8 @@ __device__ __forceinline__ void zsum_store(const ZSum& zs, int64_t off, const f3
   *reinterpret_cast<f32x4*>(zs.out + off) = v;
 }
 
-template <bool SUM>
-__device__ __forceinline__ void zrow_load(const float* __restrict__ Bz, const ZSum& zs, int64_t rr,
-                                          f32x4& z0, f32x4& z1) {
-  if (!SUM) {
-    z0 = *reinterpret_cast<const f32x4*>(Bz + rr * 8);
-    z1 = *reinterpret_cast<const f32x4*>(Bz + rr * 8 + 4);
-    return;
-  }
+// Z's row rr as the fixed-order sum of its parts
+__device__ __forceinline__ void zsum_row_load(const ZSum& zs, int64_t rr, f32x4& z0, f32x4& z1) {
   z0 = *reinterpret_cast<const f32x4*>(zs.p[0] + rr * 8);
   z1 = *reinterpret_cast<const f32x4*>(zs.p[0] + rr * 8 + 4);
   for (int i = 1; i < zs.count; ++i) {
@@ -480,18 +477,51 @@ __device__ __forceinline__ void zrow_load(const float* __restrict__ Bz, const ZS
   }
 }
 
-template <int TS_U, bool SUM>
-__global__ __launch_bounds__(256) void ts_tn_stream_kernel(BlockList A, const float* __restrict__ Bz,
-                                                           int64_t n, int64_t rows_per_chunk,
-                                                           double* __restrict__ partial,
-                                                           const int* cond, ZSum zs) {
+// One row of the streaming Grams: this lane's 4 columns of its block against the 8 of Z.
+__device__ __forceinline__ void tn_fma(float (&acc)[4][8], const f32x4& a, const f32x4& z0,
+                                       const f32x4& z1) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc[i][j] += a[i] * z0[j];
+      acc[i][4 + j] += a[i] * z1[j];
+    }
+}
+
+// The streaming Grams' tail: columns [J0, J0 + 8) of a lane's 4 x W sums in fp64 through the
+// fixed reduce-scatter over the 32 row lanes, after which lane rl holds entry
+// e = bitrev5(rl) = (i, j) = (e >> 3, e & 7) of its column half h; out: the block's 64 entries.
+template <int J0, int W>
+__device__ __forceinline__ void tn_fold_store(const float (&acc)[4][W], int rl, int h,
+                                              double* __restrict__ out) {
+  double v[32];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[i * 8 + j] = (double)acc[i][J0 + j];
+  rs_step<0, 16>(v, rl);
+  rs_step<1, 8>(v, rl);
+  rs_step<2, 4>(v, rl);
+  rs_step<3, 2>(v, rl);
+  rs_step<4, 1>(v, rl);
+  const int e = ((rl & 1) << 4) | ((rl & 2) << 2) | (rl & 4) | ((rl & 8) >> 2) | ((rl & 16) >> 4);
+  out[32 * h + e] = v[0];
+}
+
+// The streaming Gram in its Z-sum form: no LDS staging (Z is summed per lane), no barrier.
+template <int TS_U>
+__global__ __launch_bounds__(256) void ts_tn_zsum_kernel(BlockList A, int64_t n,
+                                                         int64_t rows_per_chunk,
+                                                         double* __restrict__ partial,
+                                                         const int* cond, ZSum zs) {
   if (cond && *cond == 0) return;
   const int lane = threadIdx.x & 63;
   const int blk = (int)blockIdx.y * 4 + (threadIdx.x >> 6);
   if (blk >= A.count) return;  // wave-uniform; no block barrier below
   const int h = lane >> 5, rl = lane & 31;
-  // SUM: the last block is Z (= the sums): this wave takes its A rows from them and stores them
-  const bool zblk = SUM && blk == A.count - 1;
+  // the last block is Z (= the sums): this wave takes its A rows from them and stores them
+  const bool zblk = blk == A.count - 1;
   const float* ab = (zblk ? A.blk[0] : A.blk[blk]) + 4 * h;
   const int64_t c0 = (int64_t)blockIdx.x * rows_per_chunk;
   int64_t c1 = c0 + rows_per_chunk;
@@ -508,7 +538,7 @@ __global__ __launch_bounds__(256) void ts_tn_stream_kernel(BlockList A, const fl
     for (int u = 0; u < TS_U; ++u) {
       const int64_t rr = r + 32 * u + rl;
       if (!zblk) a[u] = *reinterpret_cast<const f32x4*>(ab + rr * 8);
-      zrow_load<SUM>(Bz, zs, rr, z0[u], z1[u]);
+      zsum_row_load(zs, rr, z0[u], z1[u]);
     }
     if (zblk) {
 #pragma unroll
@@ -519,56 +549,31 @@ __global__ __launch_bounds__(256) void ts_tn_stream_kernel(BlockList A, const fl
       }
     }
 #pragma unroll
-    for (int u = 0; u < TS_U; ++u)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j] += a[u][i] * z0[u][j];
-          acc[i][4 + j] += a[u][i] * z1[u][j];
-        }
+    for (int u = 0; u < TS_U; ++u) tn_fma(acc, a[u], z0[u], z1[u]);
   }
   for (; r < c1; r += 32) {
     const int64_t rr = r + rl;
     if (rr < c1) {
       f32x4 y0, y1, a1;
-      zrow_load<SUM>(Bz, zs, rr, y0, y1);
+      zsum_row_load(zs, rr, y0, y1);
       if (zblk) {
         a1 = h ? y1 : y0;
         zsum_store(zs, rr * 8 + 4 * h, a1);
       } else {
         a1 = *reinterpret_cast<const f32x4*>(ab + rr * 8);
       }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j] += a1[i] * y0[j];
-          acc[i][4 + j] += a1[i] * y1[j];
-        }
+      tn_fma(acc, a1, y0, y1);
     }
   }
-  double v[32];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[i * 8 + j] = (double)acc[i][j];
-  rs_step<0, 16>(v, rl);
-  rs_step<1, 8>(v, rl);
-  rs_step<2, 4>(v, rl);
-  rs_step<3, 2>(v, rl);
-  rs_step<4, 1>(v, rl);
-  // lane rl now holds entry e = bitrev5(rl) = (i, j) = (e >> 3, e & 7) of its column half
-  const int e = ((rl & 1) << 4) | ((rl & 2) << 2) | (rl & 4) | ((rl & 8) >> 2) | ((rl & 16) >> 4);
   double* out = partial + (int64_t)blockIdx.x * ((int64_t)A.count * 8) * 8;
-  out[(int64_t)blk * 64 + 32 * h + e] = v[0];
+  tn_fold_store<0>(acc, rl, h, out + (int64_t)blk * 64);
 }
 
 // The streaming Gram with Z's rows staged once per workgroup through LDS (the 4 waves of a
 // workgroup take 4 basis blocks over the same rows, so each used to load the same 32-B Z row
 // per lane and row step: twice the block's own bytes through L1).  Double-buffered, the next
-// step's A rows and Z piece in flight across the barrier; same products in the same order as
-// ts_tn_stream_kernel<TS_U, false> (bit-identical Grams).  N2V2R_TN_LDS=0: the unstaged form.
+// step's A rows and Z piece in flight across the barrier; the products and their order are
+// those of ts_tn_zsum_kernel on a stored Z (tn_fma per row, tn_fold_store).
 template <int TS_U>
 __global__ __launch_bounds__(256) void ts_tn_stream_lds_kernel(BlockList A, const float* __restrict__ Bz,
                                                                int64_t n, int64_t rows_per_chunk,
@@ -615,13 +620,7 @@ __global__ __launch_bounds__(256) void ts_tn_stream_lds_kernel(BlockList A, cons
       for (int u = 0; u < TS_U; ++u) {
         const int lr = 32 * u + rl;
         const f32x4 z0 = zst[buf][lr * 2], z1 = zst[buf][lr * 2 + 1];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            acc[i][j] += a[u][i] * z0[j];
-            acc[i][4 + j] += a[u][i] * z1[j];
-          }
+        tn_fma(acc, a[u], z0, z1);
       }
     }
   }
@@ -632,34 +631,32 @@ __global__ __launch_bounds__(256) void ts_tn_stream_lds_kernel(BlockList A, cons
       const f32x4 y0 = *reinterpret_cast<const f32x4*>(Bz + rr * 8);
       const f32x4 y1 = *reinterpret_cast<const f32x4*>(Bz + rr * 8 + 4);
       const f32x4 a1 = *reinterpret_cast<const f32x4*>(ab + rr * 8);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j] += a1[i] * y0[j];
-          acc[i][4 + j] += a1[i] * y1[j];
-        }
+      tn_fma(acc, a1, y0, y1);
     }
   }
-  double v[32];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[i * 8 + j] = (double)acc[i][j];
-  rs_step<0, 16>(v, rl);
-  rs_step<1, 8>(v, rl);
-  rs_step<2, 4>(v, rl);
-  rs_step<3, 2>(v, rl);
-  rs_step<4, 1>(v, rl);
-  const int e = ((rl & 1) << 4) | ((rl & 2) << 2) | (rl & 4) | ((rl & 8) >> 2) | ((rl & 16) >> 4);
   double* out = partial + (int64_t)blockIdx.x * ((int64_t)A.count * 8) * 8;
-  out[(int64_t)blk * 64 + 32 * h + e] = v[0];
+  tn_fold_store<0>(acc, rl, h, out + (int64_t)blk * 64);
 }
 
 // Gram-kernel selection for 8-wide blocks: the streaming form (about 4096 waves, chunks of at
 // least 256 rows); the line form where its partials would not fit
 #define TN_STREAM_WAVES 4096
 #define TN_STREAM_MIN_ROWS 256
+
+// The streaming forms' chunk plan: about `waves` waves over `blocks` basis blocks, chunks of
+// TN_STREAM_MIN_ROWS .. TS_MAX_CHUNK rows (a multiple of 32), a multiple of 8 chunks before the
+// rows are rounded.  Returns the chunk count and leaves the rows per chunk in *rows; the caller
+// checks its partial buffer and *rows <= TS_MAX_CHUNK.
+static int64_t stream_chunks(int64_t n, int waves, int blocks, int64_t* rows) {
+  int64_t chunks = (waves + blocks - 1) / blocks;
+  const int64_t lo = (n + TS_MAX_CHUNK - 1) / TS_MAX_CHUNK,
+                hi = (n + TN_STREAM_MIN_ROWS - 1) / TN_STREAM_MIN_ROWS;
+  if (chunks > hi) chunks = hi;
+  if (chunks < lo) chunks = lo;
+  chunks = (chunks + 7) & ~(int64_t)7;
+  *rows = ((n + chunks - 1) / chunks + 31) & ~(int64_t)31;
+  return (n + *rows - 1) / *rows;
+}
 
 static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n,
                                double* partial, size_t partial_elems, double* out,
@@ -671,14 +668,7 @@ static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n
     // (<= 4 blocks -- the local pass -- aim at half the waves: longer chunks, half the partials
     // to reduce; cfg4 Gram 30.1 -> 28.4 us and reduce 7.0 -> 5.0 us per pass, 1024 / 8192 worse;
     // profiles/r04_tn_small_waves.txt)
-    s_chunks = ((A.count <= 4 ? TN_STREAM_WAVES / 2 : TN_STREAM_WAVES) + A.count - 1) / A.count;
-    const int64_t lo = (n + TS_MAX_CHUNK - 1) / TS_MAX_CHUNK,
-                  hi = (n + TN_STREAM_MIN_ROWS - 1) / TN_STREAM_MIN_ROWS;
-    if (s_chunks > hi) s_chunks = hi;
-    if (s_chunks < lo) s_chunks = lo;
-    s_chunks = (s_chunks + 7) & ~(int64_t)7;
-    s_rows = ((n + s_chunks - 1) / s_chunks + 31) & ~(int64_t)31;
-    s_chunks = (n + s_rows - 1) / s_rows;
+    s_chunks = stream_chunks(n, A.count <= 4 ? TN_STREAM_WAVES / 2 : TN_STREAM_WAVES, A.count, &s_rows);
     // partials must fit the buffer; otherwise the line form below takes it
     if ((size_t)(s_chunks * ca * cb) > partial_elems || s_rows > TS_MAX_CHUNK) s_chunks = 0;
   }
@@ -686,10 +676,9 @@ static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n
     const int64_t elems = (int64_t)ca * cb;
     const int64_t nchunks = s_chunks, rows_per_chunk = s_rows;
     const dim3 grid((unsigned)nchunks, (unsigned)((A.count + 3) / 4));
-    const ZSum none{};
     if (zs && zs->count > 0)
-      hipLaunchKernelGGL((ts_tn_stream_kernel<4, true>), grid, dim3(256), 0, stream, A, B.blk[0],
-                         n, rows_per_chunk, partial, cond, *zs);
+      hipLaunchKernelGGL((ts_tn_zsum_kernel<4>), grid, dim3(256), 0, stream, A, n, rows_per_chunk,
+                         partial, cond, *zs);
     else
       hipLaunchKernelGGL((ts_tn_stream_lds_kernel<4>), grid, dim3(256), 0, stream, A, B.blk[0],
                          n, rows_per_chunk, partial, cond);
@@ -797,9 +786,9 @@ extern "C" hipError_t n2v2r_launch_ts_tn_zsum(const BlockList& A, int64_t n, con
   return launch_ts_tn(A, B, n, partial, partial_elems, out, nullptr, &zs, stream);
 }
 
-// ---- paired full passes (deferred reorthogonalisation, engine.cpp Eig::pair_pass) ----------
+// ---- paired full passes (deferred reorthogonalisation, solver.cpp Eig::pair_pass) ----------
 // Two right-hand sides in one read of the basis: out = [A]^T [Za Zb] as two Gram arrays,
-// out[r][blk][64] (r = 0: Za, 1: Zb), each block's 8 x 8 in the layout of ts_tn_stream_kernel
+// out[r][blk][64] (r = 0: Za, 1: Zb), each block's 8 x 8 in the layout of the one-sided kernels
 // (row-major (blk * 8 + i, j)).  Same streaming form: one wave per (basis block, row chunk), a
 // lane owns 4 columns of its block over rows rl, rl + 32, ..., fp32 products of at most
 // TS_MAX_CHUNK / 32 rows per lane, then a fixed fp64 reduce-scatter over the 32 row lanes.
@@ -884,25 +873,11 @@ __global__ __launch_bounds__(256) void ts_tn_stream2_kernel(BlockList A, const f
               *reinterpret_cast<const f32x4*>(Zb + rr * 8 + 4));
     }
   }
-  // one right-hand side at a time through the fixed fp64 reduce-scatter (as ts_tn_stream_kernel:
-  // lane rl ends with entry bitrev5(rl) = (i, j) of its column half), so only 32 fp64 values are
-  // live at once (a 64-value fold held 144 VGPRs: 3 waves per SIMD)
-  const int e = ((rl & 1) << 4) | ((rl & 2) << 2) | (rl & 4) | ((rl & 8) >> 2) | ((rl & 16) >> 4);
+  // one right-hand side at a time through the fixed fp64 reduce-scatter, so only 32 fp64 values
+  // are live at once (a 64-value fold held 144 VGPRs: 3 waves per SIMD)
   double* out = partial + (int64_t)blockIdx.x * ((int64_t)A.count * 128);
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    double v[32];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[i * 8 + j] = (double)acc[i][8 * r + j];
-    rs_step<0, 16>(v, rl);
-    rs_step<1, 8>(v, rl);
-    rs_step<2, 4>(v, rl);
-    rs_step<3, 2>(v, rl);
-    rs_step<4, 1>(v, rl);
-    out[((int64_t)r * A.count + blk) * 64 + 32 * h + e] = v[0];
-  }
+  tn_fold_store<0>(acc, rl, h, out + (int64_t)blk * 64);
+  tn_fold_store<8>(acc, rl, h, out + ((int64_t)A.count + blk) * 64);
 }
 
 // out[2][A.count][64] = [A]^T [Za Zb] (fp64, rows over ranks NOT summed here)
@@ -911,14 +886,8 @@ extern "C" hipError_t n2v2r_launch_ts_tn2(const BlockList& A, const float* Za, c
                                           double* out, hipStream_t stream) {
   if (A.width != 8 || A.count < 1 || n < 1) return hipErrorInvalidValue;
   const int64_t elems = (int64_t)A.count * 128;
-  int64_t s_chunks = (TN_STREAM_WAVES + A.count - 1) / A.count;
-  const int64_t lo = (n + TS_MAX_CHUNK - 1) / TS_MAX_CHUNK,
-                hi = (n + TN_STREAM_MIN_ROWS - 1) / TN_STREAM_MIN_ROWS;
-  if (s_chunks > hi) s_chunks = hi;
-  if (s_chunks < lo) s_chunks = lo;
-  s_chunks = (s_chunks + 7) & ~(int64_t)7;
-  const int64_t s_rows = ((n + s_chunks - 1) / s_chunks + 31) & ~(int64_t)31;
-  s_chunks = (n + s_rows - 1) / s_rows;
+  int64_t s_rows = 0;
+  const int64_t s_chunks = stream_chunks(n, TN_STREAM_WAVES, A.count, &s_rows);
   if ((size_t)(s_chunks * elems) > partial_elems || s_rows > TS_MAX_CHUNK) return hipErrorNotSupported;
   const dim3 grid((unsigned)s_chunks, (unsigned)((A.count + 3) / 4));
   if (basis_nt(n, A.count))
@@ -938,12 +907,39 @@ extern "C" hipError_t n2v2r_launch_ts_tn2(const BlockList& A, const float* Za, c
 // products are below the threshold squared), written over Za's rows of Zb's Gram.  Ra: the
 // first pass's R (rsave; identity when that pass applied nothing) -- reset to the identity here
 // for the next pair.  One 256-thread workgroup.
+// pair_fixup: the arithmetic, by all 256 threads.  ca, cb: the c old rows of the two Grams (LDS);
+// zazb: Za^T Zb (8 x 8: row i of Za, column j of Zb); rr: Ra (LDS, published by the caller's
+// barrier); part (4 x 64) and dr (64): LDS scratch.  Thread tid < 8 ends with column tid of D in d.
+__device__ __forceinline__ void pair_fixup(const double* ca, const double* cb, int c,
+                                           const double* zazb, const double* rr, double* part,
+                                           double* dr, int tid, double (&d)[8]) {
+  {
+    const int q = tid >> 6, e = tid & 63, i = e >> 3, j = e & 7;
+    double s = 0.0;
+    for (int r = q; r < c; r += 4) s += ca[r * 8 + i] * cb[r * 8 + j];
+    part[q * 64 + e] = s;
+  }
+  __syncthreads();
+  if (tid < 64)  // Za^T Zb - Ca^T Cb, fixed order
+    dr[tid] = zazb[tid] - ((part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]));
+  __syncthreads();
+  if (tid < 8) {  // column tid: forward substitution Ra^T d = dr (Ra upper triangular)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      double v = dr[k * 8 + tid];
+#pragma unroll
+      for (int m = 0; m < k; ++m) v -= rr[m * 8 + k] * d[m];
+      d[k] = v / rr[k * 8 + k];
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void pair_fixup_kernel(double* __restrict__ g2, int nblk_all,
                                                          int nq_old, double* __restrict__ ra) {
   // LDS: Ca rows | Cb rows (nq_old * 64 fp64 each), staged with all loads of a thread in flight
   // (a thread-per-entry loop over global rows waited out one load per row: 35 us at cfg2)
   extern __shared__ double fx[];
-  __shared__ double part[4][64], dr[64], rr[64];
+  __shared__ double part[256], dr[64], rr[64];
   const int tid = threadIdx.x;
   const int nr8 = nq_old * 64;
   const double* ga = g2;                          // [nblk_all][64]: Za's Gram
@@ -954,25 +950,9 @@ __global__ __launch_bounds__(256) void pair_fixup_kernel(double* __restrict__ g2
   }
   if (tid < 64) rr[tid] = ra[tid];
   __syncthreads();
-  {
-    const int q = tid >> 6, e = tid & 63, i = e >> 3, j = e & 7;
-    double s = 0.0;
-    for (int r = q; r < nq_old * 8; r += 4) s += fx[r * 8 + i] * fx[nr8 + r * 8 + j];
-    part[q][e] = s;
-  }
-  __syncthreads();
-  if (tid < 64)  // Za^T Zb (row i of Za, column j of Zb) - Ca^T Cb, fixed order
-    dr[tid] = gb[(int64_t)nq_old * 64 + tid] - ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]));
-  __syncthreads();
-  if (tid < 8) {  // column tid: forward substitution Ra^T d = dr (Ra upper triangular)
-    double d[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      double v = dr[k * 8 + tid];
-#pragma unroll
-      for (int m = 0; m < k; ++m) v -= rr[m * 8 + k] * d[m];
-      d[k] = v / rr[k * 8 + k];
-    }
+  double d[8];
+  pair_fixup(fx, fx + nr8, nq_old * 8, gb + (int64_t)nq_old * 64, rr, part, dr, tid, d);
+  if (tid < 8) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) gb[(int64_t)nq_old * 64 + k * 8 + tid] = d[k];
   }
@@ -1463,96 +1443,7 @@ extern "C" hipError_t n2v2r_launch_pip_apply(const BlockList& QZ, const float* F
   return launch_nn(QZ, F, b, Z, none, 1.f, 0.f, n, p.cond, p.flags, p.seed, p.row0, stream);
 }
 
-// ----------------------------------------------------------------------------- small ops
-// fp64 -> fp32 copy of a (rows x cols) matrix with optional negation (CGS coefficients).
-__global__ void f64_to_f32_kernel(const double* __restrict__ in, float* __restrict__ out,
-                                  int64_t elems, float scale, const int* cond) {
-  if (cond && *cond == 0) return;
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < elems) out[e] = scale * (float)in[e];
-}
-
-extern "C" hipError_t n2v2r_launch_f64_to_f32(const double* in, float* out, int64_t elems,
-                                              float scale, const int* cond, hipStream_t stream) {
-  hipLaunchKernelGGL(f64_to_f32_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0,
-                     stream, in, out, elems, scale, cond);
-  return hipGetLastError();
-}
-
-// Cholesky G = R^T R of a b x b fp64 Gram matrix and Rinv = R^{-1} (fp32, row-major b x b),
-// one 1024-thread workgroup, every step parallel over the trailing b x b entries.
-// A pivot below 1e-10 * max diag marks a rank-deficient column: its R row becomes the unit row,
-// its Rinv column is zeroed and flags[j] / *any_flag are set.
-__global__ __launch_bounds__(1024) void chol_inv_kernel(const double* __restrict__ G, int b,
-                                                        float* __restrict__ Rinv, int* flags,
-                                                        int* any_flag) {
-  __shared__ double R[64][65];
-  __shared__ double X[64][65];
-  __shared__ double piv[64];
-  __shared__ int bad[64];
-  __shared__ double dmax;
-  const int tid = threadIdx.x;
-  const int nt = blockDim.x;
-  for (int e = tid; e < b * b; e += nt) {
-    const int r = e / b, c = e % b;
-    R[r][c] = 0.5 * (G[r * b + c] + G[c * b + r]);
-    X[r][c] = (r == c) ? 1.0 : 0.0;
-  }
-  if (tid < 64) bad[tid] = 0;
-  __syncthreads();
-  if (tid < 64) {
-    double m = (tid < b) ? R[tid][tid] : 0.0;
-    for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-    if (tid == 0) dmax = m;
-  }
-  __syncthreads();
-  const double tiny = 1e-10 * dmax;
-  // right-looking: row j of R = (row j of the Schur complement) / sqrt(pivot)
-  for (int j = 0; j < b; ++j) {
-    if (tid == 0) {
-      const double p = R[j][j];
-      if (!(p > tiny)) {
-        bad[j] = 1;
-        piv[j] = 0.0;
-      } else {
-        piv[j] = sqrt(p);
-      }
-    }
-    __syncthreads();
-    const double pj = piv[j];
-    const int isbad = bad[j];
-    // scale row j (c >= j)
-    for (int c = j + tid; c < b; c += nt) R[j][c] = isbad ? (c == j ? 1.0 : 0.0) : (c == j ? pj : R[j][c] / pj);
-    __syncthreads();
-    // trailing update R[r][c] -= R[j][r] R[j][c], j < r <= c
-    const int m = b - j - 1;
-    for (int e = tid; e < m * m; e += nt) {
-      const int r = j + 1 + e / m, c = j + 1 + e % m;
-      if (c >= r) R[r][c] -= R[j][r] * R[j][c];
-    }
-    __syncthreads();
-  }
-  // Gauss-Jordan on [R | I] from the last row up: X <- R^{-1}
-  for (int j = b - 1; j >= 0; --j) {
-    const double inv = 1.0 / R[j][j];
-    for (int c = tid; c < b; c += nt) X[j][c] *= inv;
-    __syncthreads();
-    for (int e = tid; e < j * b; e += nt) {
-      const int r = e / b, c = e % b;
-      X[r][c] -= R[r][j] * X[j][c];
-    }
-    __syncthreads();
-  }
-  int any = 0;
-  for (int j = 0; j < b; ++j) any |= bad[j];
-  for (int e = tid; e < b * b; e += nt) {
-    const int r = e / b, c = e % b;
-    Rinv[e] = bad[c] ? 0.f : (float)X[r][c];
-  }
-  if (tid < b) flags[tid] = bad[tid];
-  if (tid == 0) *any_flag = any;
-}
-
+// ----------------------------------------------------------------------------- pip_chol
 // Fused block classical Gram-Schmidt + Cholesky QR ("Pythagorean" form): given
 // G = [Q Z]^T Z ((c + b) x b, fp64) with C = Q^T Z (first c rows) and Z^T Z (last b rows),
 // P = Z^T Z - C^T C is the Gram matrix of Z - Q C.  This kernel forms P (1024 threads, the
@@ -1713,11 +1604,11 @@ __global__ __launch_bounds__(1024) void pip_chol_kernel(const double* __restrict
       // row k of R in LDS holds its values after step k - 1 (written before the barrier)
       const double d = R[k][k];
       const double zz = zzd[k];
-      const bool cn = !(d > PIP_CANCEL * zz);  // (a later pass refills: see pip_fused_kernel)
+      const bool cn = !(d > PIP_CANCEL * zz);  // (a later pass refills: see pip_factor)
       const bool isbad = !(zz > zfloor) || !(d == d) || (cn && !first);
       const bool cj = !isbad && cn;
       const double pk = isbad ? 1.0 : sqrt(cj ? PIP_CANCEL * zz : d);
-      if (own && ei == k) {  // (a clamped column is decoupled: see pip_fused_kernel)
+      if (own && ei == k) {  // (a clamped column is decoupled: see pip_factor)
         v = (isbad || cj) ? (ej == k ? pk : 0.0) : (ej == k ? pk : v / pk);
       } else if (own && ei > k && ej >= ei && !isbad && !cj) {
         v -= (R[k][ei] / pk) * (R[k][ej] / pk);
@@ -1870,22 +1761,16 @@ extern "C" hipError_t n2v2r_launch_pip_chol(const double* G, int c, int b, doubl
   return hipGetLastError();
 }
 
-extern "C" hipError_t n2v2r_launch_chol_inv(const double* G, int b, float* Rinv, int* flags,
-                                            int* any_flag, hipStream_t stream) {
-  if (b > 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(chol_inv_kernel, dim3(1), dim3(1024), 0, stream, G, b, Rinv, flags, any_flag);
-  return hipGetLastError();
-}
-
 // ----------------------------------------------------------------------------- fused PIP pass
 // One launch per BCGS-PIP pass at b = 8 (replaces pip_chol + the apply): every workgroup stages
-// the Gram G = [Q Z]^T Z ((c + 8) x 8 fp64, C = Q^T Z its first c rows) in LDS, forms
-// P = Z^T Z - C^T C (4 k-slices, fixed fold order), factors P = R^T R and inverts R with wave 0
-// lane-parallel (lane = (i, j) entry, pivots by readlane, row/column operands by shuffles: no
-// block barrier per step), then streams its 256 rows: Z <- (Z - Q C) R^{-1}, flagged columns
-// refilled by counter deviates.  Every workgroup forms the same R from the same G (the
+// the Gram G = [Q Z]^T Z ((c + 8) x 8 fp64, C = Q^T Z its first c rows) in LDS, decides which
+// blocks the pass applies (pip_select), forms P = Z^T Z - C^T C over them and factors it
+// (pip_factor), then streams its rows: Z <- (Z - Q C) R^{-1}, flagged columns refilled by counter
+// deviates (pip_row_map .. pip_finish).  Every workgroup forms the same R from the same G (the
 // factorisation is deterministic); workgroup 0 alone writes flags / any_flag / sticky / save.
 // Same pivot rule as pip_chol_kernel (PIP_CANCEL clamp; zero columns: unit row, zero R^{-1} column).
+// The paired apply further down runs the same prologue twice in one workgroup and the same row
+// stream over two right-hand sides.
 // 1 / sqrt(p), p > 0: hardware estimate + two Newton steps (full fp64 precision)
 __device__ __forceinline__ double rsq_nr(double p) {
   double r = __builtin_amdgcn_rsq(p);
@@ -1893,52 +1778,18 @@ __device__ __forceinline__ double rsq_nr(double p) {
   r = r * fma(-0.5 * p * r, r, 1.5);
   return r;
 }
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
 
-template <int QB, int NU, bool NT>
-__global__ __launch_bounds__(256) void pip_fused_kernel(BlockList Q, const float* Zin, float* Zout,
-                                                        const double* __restrict__ G, int c,
-                                                        int64_t n, const int* cond, int* flags,
-                                                        int* any_flag, double* save, int save_row0,
-                                                        int save_rows, int* sticky, uint64_t seed,
-                                                        int64_t row0, double* rsave, float skip_tol,
-                                                        int* skipped, int first) {
-  const int tid = threadIdx.x;
-  const bool lead = blockIdx.x == 0;
-  if (cond && *cond == 0) {
-    if (lead && tid < 8) flags[tid] = 0;
-    if (lead && tid == 0) *any_flag = 0;
-    return;
-  }
-  // one LDS array: gd (c + 8) x 8 fp64 | part 4 x 64 fp64 | cf c x 8 fp32 | rv 8 x 8 fp32 | mask
-  extern __shared__ __attribute__((aligned(16))) double pf_lds[];
-  double* gd = pf_lds;
-  double* part = gd + (c + 8) * 8;
-  float* cf = reinterpret_cast<float*>(part + 256);
-  float* rv = cf + c * 8;
-  int* badw = reinterpret_cast<int*>(rv + 64);
-  const int ne2 = (c + 8) * 4;  // double2 count
-  // all of a thread's G loads in flight before the first LDS write (a load -> wait -> write
-  // loop costs one L2 round trip per 256 entries: ~7 of them at c = 384)
-  for (int e0 = tid; e0 < ne2; e0 += 256 * 8) {
-    double2 t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)  // clamped, unconditional: the loads cannot sink into branches
-      t[u] = reinterpret_cast<const double2*>(G)[min(e0 + 256 * u, ne2 - 1)];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)  // past the end: the last entry again, with its own value
-      reinterpret_cast<double2*>(gd)[min(e0 + 256 * u, ne2 - 1)] = t[u];
-  }
-  __syncthreads();
-  // the basis blocks this pass applies: all, or (skip_tol > 0: selective reorthogonalisation of
-  // an in-place pass) those with max_ij |C_ij| / ||z_j|| > skip_tol; every workgroup decides
-  // alike from the same G.  C^T C sums the applied blocks only, so R factors the applied pass.
-  // (skip_tol < 0: the whole pass, all blocks or none, by |skip_tol|)
-  int* blist = badw + 4;  // compact list of applied blocks (<= N2V2R_BAND_MAXC / 8)
+// The first half of a pass's prologue, by all 256 threads of a workgroup on the staged Gram gd
+// ((c + 8) x 8 fp64 in LDS): the basis blocks this pass applies: all, or (skip_tol > 0:
+// selective reorthogonalisation of an in-place pass) those with max_ij |C_ij| / ||z_j|| >
+// skip_tol; every workgroup decides alike from the same G.  (skip_tol < 0: the whole pass, all
+// blocks or none, by |skip_tol|.)  Leaves the compact ascending list blist[0, badw[1]) and
+// badw[2] (Z's own Gram is off the identity), counts the applied blocks in skipped[1 + block]
+// (lead only), and returns whether the pass is skipped whole: nothing to apply, the caller
+// writes the skipped pass's outputs.  part: 4 x 64 fp64 of LDS, free again on return.
+__device__ __forceinline__ bool pip_select(const double* gd, int c, float skip_tol, int* skipped,
+                                           bool lead, double* part, int* badw, int* blist,
+                                           int tid) {
   const int nblk = c >> 3;
   const bool skip_whole = skip_tol < 0.f;
   skip_tol = fabsf(skip_tol);
@@ -1985,30 +1836,21 @@ __global__ __launch_bounds__(256) void pip_fused_kernel(BlockList Q, const float
     if (tid == 0) {
       badw[1] = count;
       badw[2] = zz_off;
-      badw[3] = 0;
     }
   }
   __syncthreads();
-  const int napply = badw[1];
-  if (skip_tol > 0.f) {
-    if (napply == 0 && !badw[2]) {
-      if (lead && tid < 8) flags[tid] = 0;
-      if (rsave && lead && tid < 64) rsave[tid] = (tid >> 3) == (tid & 7) ? 1.0 : 0.0;  // R = I
-      if (lead && tid == 0) {
-        *any_flag = 0;
-        if (skipped) atomicAdd(skipped, 1);
-      }
-      return;
-    }
-  }
-  if (save && lead)
-    for (int e = tid; e < save_rows * 8; e += 256) save[e] = gd[save_row0 * 8 + e];
-  // fp32 coefficients and C^T C of the applied blocks only (a selective pass applies ~7 of 48
-  // at cfg2: the pass over all of C was 2.8 us of the launch, zeroing the skipped rows 1.0)
-  for (int e = tid; e < napply * 64; e += 256) {
-    const int g = blist[e >> 6] * 64 + (e & 63);
-    cf[g] = (float)gd[g];
-  }
+  return skip_tol > 0.f && badw[1] == 0 && !badw[2];  // (uniform: every thread reads the same words)
+}
+
+// The second half: P = Z^T Z - C^T C over the applied blocks only (so R factors the applied
+// pass; a selective pass applies ~7 of 48 at cfg2), P = R^T R, R^{-1}.  Leaves rv = R^{-1}
+// (8 x 8 fp32, flagged columns zero) and badw[0] = the flagged columns' bits; the lead writes
+// flags / any_flag / sticky and, where rdst is not null, R as the lean residual estimates read
+// it.  The caller's barrier publishes them.
+__device__ __forceinline__ void pip_factor(const double* gd, int c, const int* blist, int napply,
+                                           int first, bool lead, double* rdst, int* flags,
+                                           int* any_flag, int* sticky, double* part, int* badw,
+                                           float* rv, int tid) {
   {
     const int e = tid & 63, sl = tid >> 6, i = e >> 3, j = e & 7;
     // wave sl: list entries sl, sl + 4, ...; four independent chains (rows r mod 4)
@@ -2079,13 +1921,13 @@ __global__ __launch_bounds__(256) void pip_fused_kernel(BlockList Q, const float
     // R (row-major, upper): Z - Q C = Z_out R; its columns' norms give the Krylov-Schur
     // residual estimates of the lean-image solver mode
     // (a refilled column's row is zero: the projected block has no component there)
-    if (rsave && lead) {
+    if (rdst && lead) {
       double rij = 0.0;
 #pragma unroll
       for (int r = 0; r < 8; ++r)
 #pragma unroll
         for (int q = r; q < 8; ++q) rij = (i == r && j == q) ? R[r][q] : rij;
-      rsave[tid] = ((bad >> i) & 1) ? 0.0 : rij;
+      rdst[tid] = ((bad >> i) & 1) ? 0.0 : rij;
     }
     // column j of R^{-1} by back substitution; this lane keeps entry i
     double xv[8];
@@ -2109,20 +1951,127 @@ __global__ __launch_bounds__(256) void pip_fused_kernel(BlockList Q, const float
       }
     }
   }
-  __syncthreads();
-  // rows: wave w owns rows 32 NU w .. 32 NU (w + 1) - 1 of the workgroup's 128 NU, lane =
-  // (row offset ro = lane >> 1, column half h = lane & 1) over NU 32-row parts u, so one load
-  // instruction reads 32 consecutive 32-B rows of a block (1 KB contiguous)
-  const int lane = tid & 63, h = lane & 1, ro = lane >> 1;
-  const int64_t rbase = (int64_t)blockIdx.x * (128 * NU) + (tid >> 6) * (32 * NU) + ro;
-  if (rbase >= n) return;
-  int64_t rw[NU];
-  bool okr[NU];
+}
+
+// The row stream of a pass.  Wave w owns rows 32 NU w .. 32 NU (w + 1) - 1 of the workgroup's
+// 128 NU, lane = (row offset ro = lane >> 1, column half h = lane & 1) over NU 32-row parts u,
+// so one load instruction reads 32 consecutive 32-B rows of a block (1 KB contiguous).
+// pip_row_map: this lane's rows from its first row rbase (< n).
+template <int NU>
+__device__ __forceinline__ void pip_row_map(int64_t rbase, int64_t n, int64_t (&rw)[NU],
+                                            bool (&okr)[NU]) {
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     okr[u] = rbase + 32 * u < n;
     rw[u] = okr[u] ? rbase + 32 * u : rbase;  // past the end: row rbase again, not stored
   }
+}
+
+// this lane's column half of its rows of one basis block
+template <int NU, bool NT>
+__device__ __forceinline__ void pip_load_rows(f32x4 (&a4)[NU], const float* blk,
+                                              const int64_t (&rw)[NU], int h) {
+#pragma unroll
+  for (int u = 0; u < NU; ++u)
+    a4[u] = NT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(blk + rw[u] * 8 + 4 * h))
+               : *reinterpret_cast<const f32x4*>(blk + rw[u] * 8 + 4 * h);
+}
+
+// acc -= (rows of one block) x (this half's 4 x 8 coefficients g, LDS)
+template <int NU>
+__device__ __forceinline__ void pip_subtract(float (&acc)[NU][8], const f32x4 (&a4)[NU],
+                                             const float* g) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float gv = g[m * 8 + j];
+#pragma unroll
+      for (int u = 0; u < NU; ++u) acc[u][j] -= a4[u][m] * gv;
+    }
+}
+
+// Z' = (.) R^{-1} for one row (global index grow), flagged columns refilled: this lane's half
+__device__ __forceinline__ f32x4 pip_finish(float (&acc)[8], const float* rv, int bad,
+                                            uint64_t seed, int64_t grow, int h) {
+  // the two column halves of a row sit in adjacent lanes: fold them (quad_perm [1,0,3,2])
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    acc[j] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[j]), 0xB1, 0xF, 0xF, false));
+  float o[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int jo = 4 * h + t;
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum += (j <= jo) ? acc[j] * rv[j * 8 + jo] : 0.f;
+    o[t] = ((bad >> jo) & 1) ? counter_normal(seed, (uint64_t)grow * 64 + jo) : sum;
+  }
+  return f32x4{o[0], o[1], o[2], o[3]};
+}
+
+template <int QB, int NU, bool NT>
+__global__ __launch_bounds__(256) void pip_fused_kernel(BlockList Q, const float* Zin, float* Zout,
+                                                        const double* __restrict__ G, int c,
+                                                        int64_t n, const int* cond, int* flags,
+                                                        int* any_flag, double* save, int save_row0,
+                                                        int save_rows, int* sticky, uint64_t seed,
+                                                        int64_t row0, double* rsave, float skip_tol,
+                                                        int* skipped, int first) {
+  const int tid = threadIdx.x;
+  const bool lead = blockIdx.x == 0;
+  if (cond && *cond == 0) {
+    if (lead && tid < 8) flags[tid] = 0;
+    if (lead && tid == 0) *any_flag = 0;
+    return;
+  }
+  // one LDS array: gd (c + 8) x 8 fp64 | part 4 x 64 fp64 | cf c x 8 fp32 | rv 8 x 8 fp32 | mask
+  extern __shared__ __attribute__((aligned(16))) double pf_lds[];
+  double* gd = pf_lds;
+  double* part = gd + (c + 8) * 8;
+  float* cf = reinterpret_cast<float*>(part + 256);
+  float* rv = cf + c * 8;
+  int* badw = reinterpret_cast<int*>(rv + 64);
+  int* blist = badw + 4;  // compact list of applied blocks (<= N2V2R_BAND_MAXC / 8)
+  const int ne2 = (c + 8) * 4;  // double2 count
+  // all of a thread's G loads in flight before the first LDS write (a load -> wait -> write
+  // loop costs one L2 round trip per 256 entries: ~7 of them at c = 384)
+  for (int e0 = tid; e0 < ne2; e0 += 256 * 8) {
+    double2 t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)  // clamped, unconditional: the loads cannot sink into branches
+      t[u] = reinterpret_cast<const double2*>(G)[min(e0 + 256 * u, ne2 - 1)];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)  // past the end: the last entry again, with its own value
+      reinterpret_cast<double2*>(gd)[min(e0 + 256 * u, ne2 - 1)] = t[u];
+  }
+  __syncthreads();
+  if (pip_select(gd, c, skip_tol, skipped, lead, part, badw, blist, tid)) {
+    if (lead && tid < 8) flags[tid] = 0;
+    if (rsave && lead && tid < 64) rsave[tid] = (tid >> 3) == (tid & 7) ? 1.0 : 0.0;  // R = I
+    if (lead && tid == 0) {
+      *any_flag = 0;
+      if (skipped) atomicAdd(skipped, 1);
+    }
+    return;
+  }
+  const int napply = badw[1];
+  if (save && lead)
+    for (int e = tid; e < save_rows * 8; e += 256) save[e] = gd[save_row0 * 8 + e];
+  // fp32 coefficients of the applied blocks only (the pass over all of C was 2.8 us of the
+  // launch, zeroing the skipped rows 1.0)
+  for (int e = tid; e < napply * 64; e += 256) {
+    const int g = blist[e >> 6] * 64 + (e & 63);
+    cf[g] = (float)gd[g];
+  }
+  pip_factor(gd, c, blist, napply, first, lead, rsave, flags, any_flag, sticky, part, badw, rv, tid);
+  __syncthreads();
+  const int lane = tid & 63, h = lane & 1, ro = lane >> 1;
+  const int64_t rbase = (int64_t)blockIdx.x * (128 * NU) + (tid >> 6) * (32 * NU) + ro;
+  if (rbase >= n) return;
+  int64_t rw[NU];
+  bool okr[NU];
+  pip_row_map<NU>(rbase, n, rw, okr);
   float acc[NU][8];
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
@@ -2140,60 +2089,21 @@ __global__ __launch_bounds__(256) void pip_fused_kernel(BlockList Q, const float
 #pragma unroll
     for (int b4 = 0; b4 < QB; ++b4) bi[b4] = __builtin_amdgcn_readfirstlane(blist[q + b4]);
 #pragma unroll
-    for (int b4 = 0; b4 < QB; ++b4)
+    for (int b4 = 0; b4 < QB; ++b4) pip_load_rows<NU, NT>(a4[b4], Q.blk[bi[b4]], rw, h);
 #pragma unroll
-      for (int u = 0; u < NU; ++u)
-        a4[b4][u] = NT ? __builtin_nontemporal_load(
-                             reinterpret_cast<const f32x4*>(Q.blk[bi[b4]] + rw[u] * 8 + 4 * h))
-                       : *reinterpret_cast<const f32x4*>(Q.blk[bi[b4]] + rw[u] * 8 + 4 * h);
-#pragma unroll
-    for (int b4 = 0; b4 < QB; ++b4) {
-      const float* g = cf + (bi[b4] * 8 + 4 * h) * 8;
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float gv = g[m * 8 + j];
-#pragma unroll
-          for (int u = 0; u < NU; ++u) acc[u][j] -= a4[b4][u][m] * gv;
-        }
-    }
+    for (int b4 = 0; b4 < QB; ++b4) pip_subtract<NU>(acc, a4[b4], cf + (bi[b4] * 8 + 4 * h) * 8);
   }
   for (; q < napply; ++q) {
     f32x4 a4[NU];
     const int bq = __builtin_amdgcn_readfirstlane(blist[q]);
-#pragma unroll
-    for (int u = 0; u < NU; ++u)
-      a4[u] = NT ? __builtin_nontemporal_load(
-                       reinterpret_cast<const f32x4*>(Q.blk[bq] + rw[u] * 8 + 4 * h))
-                 : *reinterpret_cast<const f32x4*>(Q.blk[bq] + rw[u] * 8 + 4 * h);
-    const float* g = cf + (bq * 8 + 4 * h) * 8;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float gv = g[m * 8 + j];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) acc[u][j] -= a4[u][m] * gv;
-      }
+    pip_load_rows<NU, NT>(a4, Q.blk[bq], rw, h);
+    pip_subtract<NU>(acc, a4, cf + (bq * 8 + 4 * h) * 8);
   }
   const int bad = badw[0];
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
-    // the two column halves of a row sit in adjacent lanes: fold them (quad_perm [1,0,3,2])
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      acc[u][j] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[u][j]), 0xB1, 0xF, 0xF, false));
-    float o[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int jo = 4 * h + t;
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) sum += (j <= jo) ? acc[u][j] * rv[j * 8 + jo] : 0.f;
-      o[t] = ((bad >> jo) & 1) ? counter_normal(seed, (uint64_t)(row0 + rw[u]) * 64 + jo) : sum;
-    }
-    if (okr[u]) *reinterpret_cast<f32x4*>(Zout + rw[u] * 8 + 4 * h) = f32x4{o[0], o[1], o[2], o[3]};
+    const f32x4 o = pip_finish(acc[u], rv, bad, seed, row0 + rw[u], h);
+    if (okr[u]) *reinterpret_cast<f32x4*>(Zout + rw[u] * 8 + 4 * h) = o;
   }
 }
 
@@ -2243,9 +2153,9 @@ extern "C" hipError_t n2v2r_launch_pip_fused(const BlockList& Q, const float* Zi
 // ------------------------------------------------------------- paired apply (Eig::pair_pass)
 // The two selective passes of a pair, Za against Q and Zb against [Q Za'], in one read of the
 // basis.  pair_plan_kernel (one workgroup) takes both passes' decisions from the pair's Grams:
-// each pass's block list, P, R and R^{-1} exactly as pip_fused_kernel's prologue takes them
-// (pair_side below is that prologue as a function), and between them Zb's Gram against the
-// corrected Za' exactly as pair_fixup_kernel forms it.  It leaves a plan in global memory:
+// each pass's block list, P, R and R^{-1} by the prologue pip_fused_kernel runs (pip_select,
+// pip_factor), and between them Zb's Gram against the corrected Za' as pair_fixup_kernel forms
+// it (pair_fixup).  It leaves a plan in global memory:
 //   words [0, 16)   nunion | bit 0: pass a skipped, 1: pass b skipped, 2: b applies Za' |
 //                   bad columns of a | of b
 //   [16, 208)       R_a^{-1}, R_b^{-1}, Zb's coefficients against Za' (8 x 8 fp32 each)
@@ -2260,152 +2170,24 @@ extern "C" hipError_t n2v2r_launch_pip_fused(const BlockList& Q, const float* Zi
 #define PAIR_PLAN_HDR 16
 #define PAIR_PLAN_LIST (PAIR_PLAN_HDR + 192)
 
-// One selective pass's prologue on its staged Gram gd ((c + 8) x 8 fp64 in LDS), by all 256
-// threads of the one workgroup: pip_fused_kernel's, statement for statement (first = 0, no
-// cond, no save).  Leaves blist[0, badw[1]), badw[0] = bad columns, badw[3] = the pass is
-// skipped whole, rv = R^{-1} (fp32) and rr = R as pip_fused_kernel's rsave gets it (the
-// identity for a skipped pass); the caller's barrier publishes them.
-__device__ __forceinline__ void pair_side(const double* gd, int c, float skip_tol, int* skipped,
-                                          int* flags, int* any_flag, int* sticky, double* part,
-                                          int* badw, int* blist, float* rv, double* rr, int tid) {
-  const int nblk = c >> 3;
-  const bool skip_whole = skip_tol < 0.f;
-  skip_tol = fabsf(skip_tol);
-  int* bflag = reinterpret_cast<int*>(part);
-  if (skip_tol > 0.f) {
-    const int lane = tid & 63;
-    const double thr = (double)skip_tol * (double)skip_tol *
-                       fmax(gd[(c + (lane & 7)) * 8 + (lane & 7)], 1e-300);
-    for (int bk = tid >> 6; bk < nblk; bk += 4) {
-      const double g = gd[bk * 64 + lane];
-      const unsigned long long bm = __ballot(g * g > thr);
-      if (lane == 0) bflag[bk] = bm != 0ull;
-    }
-    __syncthreads();
-  }
-  int zz_off = 0;
-  if (skip_tol > 0.f && tid < 64) {
-    const int i = tid >> 3, j = tid & 7;
-    zz_off = __ballot(fabs(gd[(c + i) * 8 + j] - (i == j ? 1.0 : 0.0)) > (double)skip_tol) != 0ull;
-  }
-  if (tid < 64) {
-    bool any_on = false;
-    for (int c0 = 0; c0 < nblk; c0 += 64) {
-      const int bk = c0 + tid;
-      const bool on = bk < nblk && (skip_tol <= 0.f || bflag[bk] != 0);
-      any_on |= __ballot(on) != 0ull;
-    }
-    const bool all = skip_whole && any_on;
-    int count = 0;
-    for (int c0 = 0; c0 < nblk; c0 += 64) {
-      const int bk = c0 + tid;
-      const bool on = bk < nblk && (all || skip_tol <= 0.f || bflag[bk] != 0);
-      const unsigned long long m = __ballot(on);
-      if (on) blist[count + __popcll(m & ((1ull << tid) - 1ull))] = bk;
-      if (skipped && on && skip_tol > 0.f) atomicAdd(skipped + 1 + bk, 1);  // histogram
-      count += __popcll(m);
-    }
-    if (tid == 0) {
-      badw[0] = 0;
-      badw[1] = count;
-      badw[2] = zz_off;
-      badw[3] = 0;
-    }
-  }
-  __syncthreads();
-  const int napply = badw[1];
-  if (skip_tol > 0.f && napply == 0 && !badw[2]) {  // (uniform: every thread reads the same words)
+// One selective pass's prologue in the plan's one workgroup (a later pass: first = 0; no cond, no
+// save).  Leaves blist[0, badw[1]), badw[0] = bad columns, rv = R^{-1} (fp32) and rr = R as a
+// launch of its own leaves it in rsave (the identity for a skipped pass); returns whether the
+// pass is skipped whole.  The caller's barrier publishes them.
+__device__ __forceinline__ bool pair_prologue(const double* gd, int c, float skip_tol, int* skipped,
+                                              int* flags, int* any_flag, int* sticky, double* part,
+                                              int* badw, int* blist, float* rv, double* rr, int tid) {
+  if (pip_select(gd, c, skip_tol, skipped, true, part, badw, blist, tid)) {
     if (tid < 8) flags[tid] = 0;
     if (tid < 64) rr[tid] = (tid >> 3) == (tid & 7) ? 1.0 : 0.0;
     if (tid == 0) {
       *any_flag = 0;
       if (skipped) atomicAdd(skipped, 1);
     }
-    if (tid == 0) badw[3] = 1;
-    return;
+    return true;
   }
-  {
-    const int e = tid & 63, sl = tid >> 6, i = e >> 3, j = e & 7;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    for (int q = sl; q < napply; q += 4) {
-      const double* g = gd + blist[q] * 64;
-#pragma unroll
-      for (int r = 0; r < 8; r += 4) {
-        a0 += g[r * 8 + i] * g[r * 8 + j];
-        a1 += g[(r + 1) * 8 + i] * g[(r + 1) * 8 + j];
-        a2 += g[(r + 2) * 8 + i] * g[(r + 2) * 8 + j];
-        a3 += g[(r + 3) * 8 + i] * g[(r + 3) * 8 + j];
-      }
-    }
-    part[sl * 64 + e] = (a0 + a1) + (a2 + a3);
-  }
-  __syncthreads();
-  if (tid < 64) {
-    const int i = tid >> 3, j = tid & 7;
-    const double v = 0.5 * (gd[(c + i) * 8 + j] + gd[(c + j) * 8 + i]);
-    part[tid] = v - part[tid] - part[64 + tid] - part[128 + tid] - part[192 + tid];
-  }
-  __syncthreads();
-  if (tid < 64) {
-    const int i = tid >> 3, j = tid & 7;
-    double R[8][8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-      for (int q = r; q < 8; ++q) R[r][q] = part[r * 8 + q];
-    double zmax = 0.0;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) zmax = fmax(zmax, gd[(c + r) * 8 + r]);
-    const double zfloor = 1e-30 * zmax;
-    int bad = 0, cancel = 0;
-    double rinv[8];
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) {
-      const double p = R[jj][jj];
-      const double zz = gd[(c + jj) * 8 + jj];
-      const bool cn = !(p > PIP_CANCEL * zz);
-      const bool bj = !(zz > zfloor) || !(p == p) || cn;  // (a later pass: cancelled -> refilled)
-      const bool cj = !bj && cn;
-      bad |= (int)bj << jj;
-      cancel |= (int)cj << jj;
-      const double pe = bj ? 1.0 : (cj ? PIP_CANCEL * zz : p);
-      const double r = rsq_nr(pe);
-#pragma unroll
-      for (int q = jj + 1; q < 8; ++q) R[jj][q] = (bj || cj) ? 0.0 : R[jj][q] * r;
-      R[jj][jj] = bj ? 1.0 : pe * r;
-      rinv[jj] = bj ? 1.0 : r;
-#pragma unroll
-      for (int a = jj + 1; a < 8; ++a)
-#pragma unroll
-        for (int q = a; q < 8; ++q) R[a][q] -= R[jj][a] * R[jj][q];
-    }
-    {
-      double rij = 0.0;
-#pragma unroll
-      for (int r = 0; r < 8; ++r)
-#pragma unroll
-        for (int q = r; q < 8; ++q) rij = (i == r && j == q) ? R[r][q] : rij;
-      rr[tid] = ((bad >> i) & 1) ? 0.0 : rij;
-    }
-    double xv[8];
-#pragma unroll
-    for (int a = 7; a >= 0; --a) {
-      double t = (a == j) ? 1.0 : 0.0;
-#pragma unroll
-      for (int k = a + 1; k < 8; ++k) t -= R[a][k] * xv[k];
-      xv[a] = t * rinv[a];
-    }
-    double x = xv[0];
-#pragma unroll
-    for (int a = 1; a < 8; ++a) x = (i == a) ? xv[a] : x;
-    rv[tid] = ((bad >> j) & 1) ? 0.f : (float)x;
-    if (tid == 0) badw[0] = bad;
-    if (tid < 8) flags[tid] = (bad >> tid) & 1;
-    if (tid == 0) {
-      *any_flag = (bad | cancel) != 0;
-      if ((bad | cancel) && sticky) *sticky = 1;
-    }
-  }
+  pip_factor(gd, c, blist, badw[1], 0, true, rr, flags, any_flag, sticky, part, badw, rv, tid);
+  return false;
 }
 
 __global__ __launch_bounds__(256) void pair_plan_kernel(double* __restrict__ g2, int nblk_all,
@@ -2428,28 +2210,13 @@ __global__ __launch_bounds__(256) void pair_plan_kernel(double* __restrict__ g2,
   stage_to_lds<256, 16>(gda, g2, (c + 8) * 8, tid);
   stage_to_lds<256, 16>(gdb, gb, (c + 16) * 8, tid);
   __syncthreads();
-  pair_side(gda, c, skip_tol, skipped, flags, any_flag, sticky, part, bwa, bla, rva, rra, tid);
+  const bool skip_a =
+      pair_prologue(gda, c, skip_tol, skipped, flags, any_flag, sticky, part, bwa, bla, rva, rra, tid);
   __syncthreads();
-  // Zb's Gram against the corrected Za' (pair_fixup_kernel): over all of Q's rows of both Grams
-  {
-    const int q = tid >> 6, e = tid & 63, i = e >> 3, j = e & 7;
-    double s = 0.0;
-    for (int r = q; r < c; r += 4) s += gda[r * 8 + i] * gdb[r * 8 + j];
-    part[q * 64 + e] = s;
-  }
-  __syncthreads();
-  if (tid < 64)
-    dr[tid] = gdb[c * 8 + tid] - ((part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]));
-  __syncthreads();
+  // Zb's Gram against the corrected Za': over all of Q's rows of both Grams
+  double d[8];
+  pair_fixup(gda, gdb, c, gdb + c * 8, rra, part, dr, tid, d);
   if (tid < 8) {
-    double d[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      double v = dr[k * 8 + tid];
-#pragma unroll
-      for (int m = 0; m < k; ++m) v -= rra[m * 8 + k] * d[m];
-      d[k] = v / rra[k * 8 + k];
-    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       gdb[c * 8 + k * 8 + tid] = d[k];
@@ -2457,7 +2224,8 @@ __global__ __launch_bounds__(256) void pair_plan_kernel(double* __restrict__ g2,
     }
   }
   __syncthreads();
-  pair_side(gdb, c + 8, skip_tol, skipped, flags, any_flag, sticky, part, bwb, blb, rvb, rrb, tid);
+  const bool skip_b = pair_prologue(gdb, c + 8, skip_tol, skipped, flags, any_flag, sticky, part, bwb,
+                                    blb, rvb, rrb, tid);
   for (int e = tid; e < nq_old; e += 256) umask[e] = 0;
   __syncthreads();
   const int na = bwa[1], nb = bwb[1];  // (a skipped pass has an empty list)
@@ -2482,15 +2250,15 @@ __global__ __launch_bounds__(256) void pair_plan_kernel(double* __restrict__ g2,
   if (tid == 0) {
     const bool za = nb > 0 && blb[nb - 1] == nq_old;  // (ascending: Za' can only come last)
     plan[0] = nu;
-    plan[1] = (bwa[3] ? 1 : 0) | (bwb[3] ? 2 : 0) | (za ? 4 : 0);
-    plan[2] = bwa[3] ? 0 : bwa[0];
-    plan[3] = bwb[3] ? 0 : bwb[0];
+    plan[1] = (skip_a ? 1 : 0) | (skip_b ? 2 : 0) | (za ? 4 : 0);
+    plan[2] = skip_a ? 0 : bwa[0];
+    plan[3] = skip_b ? 0 : bwb[0];
   }
   if (tid >= 4 && tid < PAIR_PLAN_HDR) plan[tid] = 0;
   float* pf = reinterpret_cast<float*>(plan);
   if (tid < 64) {
-    pf[PAIR_PLAN_HDR + tid] = bwa[3] ? 0.f : rva[tid];
-    pf[PAIR_PLAN_HDR + 64 + tid] = bwb[3] ? 0.f : rvb[tid];
+    pf[PAIR_PLAN_HDR + tid] = skip_a ? 0.f : rva[tid];
+    pf[PAIR_PLAN_HDR + 64 + tid] = skip_b ? 0.f : rvb[tid];
     pf[PAIR_PLAN_HDR + 128 + tid] = (float)gdb[c * 8 + tid];
   }
   for (int e = tid; e < umax; e += 256) plan[PAIR_PLAN_LIST + e] = e < nu ? ulist[e] : 0;
@@ -2538,11 +2306,7 @@ __global__ __launch_bounds__(256) void pip_pair_kernel(BlockList Q, float* Za, f
   if (rbase >= n) return;
   int64_t rw[NU];
   bool okr[NU];
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    okr[u] = rbase + 32 * u < n;
-    rw[u] = okr[u] ? rbase + 32 * u : rbase;
-  }
+  pip_row_map<NU>(rbase, n, rw, okr);
   float aa[NU][8], ab[NU][8];
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
@@ -2557,23 +2321,6 @@ __global__ __launch_bounds__(256) void pip_pair_kernel(BlockList Q, float* Za, f
       ab[u][4 + t] = h ? y[t] : 0.f;
     }
   }
-  auto apply = [&](float (&acc)[NU][8], const f32x4 (&a4)[NU], const float* g) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float gv = g[m * 8 + j];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) acc[u][j] -= a4[u][m] * gv;
-      }
-  };
-  auto load = [&](f32x4 (&a4)[NU], int bk) {
-#pragma unroll
-    for (int u = 0; u < NU; ++u)
-      a4[u] = NT ? __builtin_nontemporal_load(
-                       reinterpret_cast<const f32x4*>(Q.blk[bk] + rw[u] * 8 + 4 * h))
-                 : *reinterpret_cast<const f32x4*>(Q.blk[bk] + rw[u] * 8 + 4 * h);
-  };
   int q = 0;
   for (; q + QB <= nun; q += QB) {  // QB blocks x NU rows in flight
     f32x4 a4[QB][NU];
@@ -2581,43 +2328,27 @@ __global__ __launch_bounds__(256) void pip_pair_kernel(BlockList Q, float* Za, f
 #pragma unroll
     for (int b4 = 0; b4 < QB; ++b4) ue[b4] = __builtin_amdgcn_readfirstlane(ulist[q + b4]);
 #pragma unroll
-    for (int b4 = 0; b4 < QB; ++b4) load(a4[b4], ue[b4] & 0xFFFF);
+    for (int b4 = 0; b4 < QB; ++b4) pip_load_rows<NU, NT>(a4[b4], Q.blk[ue[b4] & 0xFFFF], rw, h);
 #pragma unroll
     for (int b4 = 0; b4 < QB; ++b4) {
       const float* g = coef + (q + b4) * 128 + 4 * h * 8;
-      if (ue[b4] & (1 << 16)) apply(aa, a4[b4], g);
-      if (ue[b4] & (2 << 16)) apply(ab, a4[b4], g + 64);
+      if (ue[b4] & (1 << 16)) pip_subtract<NU>(aa, a4[b4], g);
+      if (ue[b4] & (2 << 16)) pip_subtract<NU>(ab, a4[b4], g + 64);
     }
   }
   for (; q < nun; ++q) {
     f32x4 a4[NU];
     const int ue = __builtin_amdgcn_readfirstlane(ulist[q]);
-    load(a4, ue & 0xFFFF);
+    pip_load_rows<NU, NT>(a4, Q.blk[ue & 0xFFFF], rw, h);
     const float* g = coef + q * 128 + 4 * h * 8;
-    if (ue & (1 << 16)) apply(aa, a4, g);
-    if (ue & (2 << 16)) apply(ab, a4, g + 64);
+    if (ue & (1 << 16)) pip_subtract<NU>(aa, a4, g);
+    if (ue & (2 << 16)) pip_subtract<NU>(ab, a4, g + 64);
   }
-  // Z' = (.) R^{-1}, flagged columns refilled: pip_fused_kernel's epilogue
-  auto finish = [&](float (&acc)[8], const float* rv, int bad, uint64_t seed, int64_t row) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      acc[j] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[j]), 0xB1, 0xF, 0xF, false));
-    float o[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int jo = 4 * h + t;
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) sum += (j <= jo) ? acc[j] * rv[j * 8 + jo] : 0.f;
-      o[t] = ((bad >> jo) & 1) ? counter_normal(seed, (uint64_t)(row0 + row) * 64 + jo) : sum;
-    }
-    return f32x4{o[0], o[1], o[2], o[3]};
-  };
   f32x4 oa[NU];  // this lane's column half of Za' (of Za as it is when its pass is skipped)
   if (!skip_a) {
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
-      oa[u] = finish(aa[u], rva, bad_a, seed_a, rw[u]);
+      oa[u] = pip_finish(aa[u], rva, bad_a, seed_a, row0 + rw[u], h);
       if (okr[u]) *reinterpret_cast<f32x4*>(Za + rw[u] * 8 + 4 * h) = oa[u];
     }
   } else if (b_za) {
@@ -2625,10 +2356,10 @@ __global__ __launch_bounds__(256) void pip_pair_kernel(BlockList Q, float* Za, f
     for (int u = 0; u < NU; ++u) oa[u] = *reinterpret_cast<const f32x4*>(Za + rw[u] * 8 + 4 * h);
   }
   if (skip_b) return;
-  if (b_za) apply(ab, oa, cza + 4 * h * 8);
+  if (b_za) pip_subtract<NU>(ab, oa, cza + 4 * h * 8);
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
-    const f32x4 o = finish(ab[u], rvb, bad_b, seed_b, rw[u]);
+    const f32x4 o = pip_finish(ab[u], rvb, bad_b, seed_b, row0 + rw[u], h);
     if (okr[u]) *reinterpret_cast<f32x4*>(Zb + rw[u] * 8 + 4 * h) = o;
   }
 }

@@ -111,6 +111,90 @@ int n2v2r_rr_top(n2v2r_handle* h, int c, const double* H, int p, double* w, floa
   });
 }
 
+// One orthogonalisation pass at b = 8 alone (tests): the solver's launchers on host arrays.
+int n2v2r_pip_pass(n2v2r_handle* h, int64_t n, int nq, const float* Q, float* Za, float* Zb,
+                   float tau, int first, int form, uint64_t seed, double* gram, double* R,
+                   int* flags, int* any_flag, int* skipped) {
+  return guarded(h, [&]() -> int {
+    const int nz = Zb ? 2 : 1;
+    if (h->multi() || h->comm || n < 1 || nq < 1 || (nq + nz - 1) * 8 > N2V2R_BAND_MAXC || !Q || !Za ||
+        !gram || !flags || !any_flag || !skipped || (Zb && (first || form < 0 || form > 1)) ||
+        (!Zb && !R))
+      return N2V2R_ERR_BAD_ARG;
+    hipStream_t st = h->stream;
+    const size_t blk = sizeof(float) * (size_t)n * 8;
+    const int nskip = 4 + N2V2R_BAND_MAXC / 8;
+    DevBuf basis, part, g, r, words, plan;
+    basis.ensure(blk * (nq + nz));
+    // the streaming Grams' partials: their chunk plan's largest count, two right-hand sides
+    const size_t part_n =
+        (size_t)std::max<int64_t>(4096 / (nq + nz), n / 8192) * (nq + nz) * 128 + 9 * 128 * (nq + nz);
+    part.ensure(sizeof(double) * part_n);
+    g.ensure(sizeof(double) * nz * (size_t)(nq + nz) * 64);
+    r.ensure(sizeof(double) * 64);
+    words.ensure(sizeof(int) * (64 + 4 + nskip));  // flags | any_flag, sticky | skip counters
+    int* fl = words.as<int>();
+    HIPCHK(hipMemsetAsync(fl, 0, sizeof(int) * (64 + 4 + nskip), st));
+    BlockList all{};
+    all.count = nq + nz;
+    all.width = 8;
+    for (int i = 0; i < nq + nz; ++i) all.blk[i] = basis.as<float>() + (size_t)i * n * 8;
+    float* za = basis.as<float>() + (size_t)nq * n * 8;
+    float* zb = za + (size_t)n * 8;
+    HIPCHK(hipMemcpyAsync(basis.p, Q, blk * nq, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(za, Za, blk, hipMemcpyHostToDevice, st));
+    if (Zb) HIPCHK(hipMemcpyAsync(zb, Zb, blk, hipMemcpyHostToDevice, st));
+    const double eye[64] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0,
+                            0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0,
+                            0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+    HIPCHK(hipMemcpyAsync(r.p, eye, sizeof(eye), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // pageable sources: complete before the kernels
+    PipPass p;
+    p.flags = fl;
+    p.any_flag = fl + 64;
+    p.sticky = fl + 65;
+    p.seed = seed;
+    p.rsave = r.as<double>();
+    p.skip_tol = tau;
+    p.skipped = tau != 0.f ? fl + 68 : nullptr;
+    p.first = first;
+    hipError_t e;
+    bool paired = true;
+    if (!Zb) {
+      BlockList B{};
+      B.count = 1;
+      B.width = 8;
+      B.blk[0] = za;
+      e = n2v2r_launch_ts_tn(all, B, n, part.as<double>(), part_n, g.as<double>(), nullptr, st);
+      all.count = nq;
+      if (e == hipSuccess)
+        e = n2v2r_launch_pip_fused(all, za, za, g.as<double>(), nq * 8, n, p, st);
+    } else {
+      e = n2v2r_launch_ts_tn2(all, za, zb, n, part.as<double>(), part_n, g.as<double>(), st);
+      if (e == hipSuccess) {
+        PipPass pz = p;  // Zb's pass: the next seed, no R
+        pz.seed = seed + 1;
+        pz.rsave = nullptr;
+        if (form == 1) plan.ensure(sizeof(int) * N2V2R_PAIR_PLAN_WORDS);
+        paired = pair_apply_launches(all, g.as<double>(), n, p, pz, form == 1 ? plan.as<int>() : nullptr,
+                                     plan.bytes, st) == (form == 1);
+      }
+    }
+    if (e == hipErrorInvalidValue || e == hipErrorNotSupported) return N2V2R_ERR_BAD_ARG;
+    HIPCHK(e);
+    HIPCHK(hipMemcpyAsync(Za, za, blk, hipMemcpyDeviceToHost, st));
+    if (Zb) HIPCHK(hipMemcpyAsync(Zb, zb, blk, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(gram, g.p, sizeof(double) * nz * (size_t)(nq + nz) * 64,
+                          hipMemcpyDeviceToHost, st));
+    if (!Zb) HIPCHK(hipMemcpyAsync(R, r.p, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(flags, fl, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(any_flag, fl + 64, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(skipped, fl + 68, sizeof(int) * (nq + nz), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return paired ? N2V2R_OK : N2V2R_ERR_BAD_ARG;  // (form 1 where the plan does not fit)
+  });
+}
+
 int n2v2r_rr_band_top(n2v2r_handle* h, int c, int kp, const double* hband, int64_t hband_len,
                       const double* theta_prev, int p, double* w, float* S) {
   if (h && h->multi()) h = h->ranks[0];  // (diagnostics: rank 0)

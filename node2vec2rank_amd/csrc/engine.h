@@ -734,6 +734,12 @@ inline double spmm_algo_bytes(int64_t nnz, bool unit, int64_t rows, int64_t pane
 
 // the tiled column-block SpMM wanted at panel width b (solver.cpp)
 bool col_blocks_wanted(const n2v2r_handle* h, int b);
+// the launches of a pair's two selective passes after its Gram (solver.cpp: Eig::pair_pass and
+// the diagnostic n2v2r_pip_pass).  all: Q's blocks, then Za, then Zb; pa.rsave: R of Za's pass;
+// plan: the paired apply's plan buffer, or nullptr for the three-launch form.  true: the paired
+// apply ran
+bool pair_apply_launches(const BlockList& all, double* g2, int64_t n, const PipPass& pa,
+                         const PipPass& pz, int* plan, size_t plan_bytes, hipStream_t st);
 // a new single-GPU handle on `device` (engine.cpp); nullptr on failure
 n2v2r_handle* new_handle(int device);
 // Local embedding rows of a (rank) handle into Y with layer k's block at Y + k * layer_stride

@@ -167,6 +167,32 @@ struct ReadBack {
   }
 };
 
+// The two selective passes of a pair after its Gram g2 = [Q Za Zb]^T [Za Zb] (ts_tn2): Za's pass
+// against Q, Zb's Gram against the corrected Za (pair_fixup), Zb's pass against [Q Za].  With a
+// plan buffer, and where the plan fits it, one small launch plans both and one applies them in
+// one read of Q (pip_pair: returns true); else the three launches.
+bool pair_apply_launches(const BlockList& all, double* g2, int64_t n, const PipPass& pa,
+                         const PipPass& pz, int* plan, size_t plan_bytes, hipStream_t st) {
+  const int nq_old = all.count - 2;
+  float* za = const_cast<float*>(all.blk[nq_old]);
+  float* zb = const_cast<float*>(all.blk[nq_old + 1]);
+  BlockList q = all;
+  q.count = nq_old;
+  if (plan) {
+    const hipError_t pe = n2v2r_launch_pip_pair(q, za, zb, g2, n, pa.flags, pa.any_flag, pa.sticky,
+                                                pa.seed, pz.seed, pa.row0, pa.skip_tol, pa.skipped,
+                                                plan, plan_bytes, st);
+    if (pe == hipSuccess) return true;
+    if (pe != hipErrorNotSupported) throw HipFail{pe, "n2v2r_launch_pip_pair"};
+  }
+  HIPCHK(n2v2r_launch_pip_fused(q, za, za, g2, nq_old * 8, n, pa, st));
+  HIPCHK(n2v2r_launch_pair_fixup(g2, nq_old + 2, nq_old, pa.rsave, st));
+  q.count = nq_old + 1;
+  HIPCHK(n2v2r_launch_pip_fused(q, zb, zb, g2 + (size_t)(nq_old + 2) * 64, (nq_old + 1) * 8, n, pz,
+                                st));
+  return false;
+}
+
 // ---- the eigensolver ----------------------------------------------------------------------
 struct Eig {
   n2v2r_handle* h;
@@ -840,34 +866,18 @@ struct Eig {
     double* g2 = h->ews.g2.as<double>();
     const double t0 = now_ms();
     lds_poison();
-    const hipError_t e = n2v2r_launch_ts_tn2(blocks(all, 0, nq_old + 2), deferred, zb, n, part_p,
-                                             part_n, g2, st);
+    const BlockList L = blocks(all, 0, nq_old + 2);
+    const hipError_t e = n2v2r_launch_ts_tn2(L, deferred, zb, n, part_p, part_n, g2, st);
     if (e == hipErrorNotSupported) return false;
     if (e != hipSuccess) throw HipFail{e, "n2v2r_launch_ts_tn2"};
     if (h->comm) h->allreduce_f64(g2, 2 * (size_t)(nq_old + 2) * 64);
     // Za's selective pass (its R kept for the fix-up), then Zb's; each with its refill seed
-    double* ra = h->ews.pair_ra.as<double>();
-    PipPass pa = selective_pass(any_p + 3, ra), pz = selective_pass(any_p + 3);
+    PipPass pa = selective_pass(any_p + 3, h->ews.pair_ra.as<double>()),
+            pz = selective_pass(any_p + 3);
     pa.seed = next_fill_seed();
     pz.seed = next_fill_seed();
-    if (pair_apply) {
-      // both in one read of the basis
-      const hipError_t pe = n2v2r_launch_pip_pair(
-          blocks(basis, 0, nq_old), deferred, zb, g2, n, pa.flags, pa.any_flag, pa.sticky, pa.seed,
-          pz.seed, row0, reorth_tol, pa.skipped, h->ews.pair_plan.as<int>(),
-          h->ews.pair_plan.bytes, st);
-      if (pe == hipSuccess) {
-        t_ortho += now_ms() - t0;
-        deferred = nullptr;
-        return true;
-      }
-      if (pe != hipErrorNotSupported) throw HipFail{pe, "n2v2r_launch_pip_pair"};
-    }
-    HIPCHK(n2v2r_launch_pip_fused(blocks(basis, 0, nq_old), deferred, deferred, g2, nq_old * b, n,
-                                  pa, st));
-    HIPCHK(n2v2r_launch_pair_fixup(g2, nq_old + 2, nq_old, ra, st));
-    HIPCHK(n2v2r_launch_pip_fused(blocks(basis, 0, nq_old + 1), zb, zb,
-                                  g2 + (size_t)(nq_old + 2) * 64, (nq_old + 1) * b, n, pz, st));
+    pair_apply_launches(L, g2, n, pa, pz, pair_apply ? h->ews.pair_plan.as<int>() : nullptr,
+                        h->ews.pair_plan.bytes, st);
     t_ortho += now_ms() - t0;
     deferred = nullptr;
     return true;
