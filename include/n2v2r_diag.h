@@ -57,6 +57,32 @@ int n2v2r_pip_pass(n2v2r_handle* h, int64_t n, int nq, const float* Q, float* Za
                    float tau, int first, int form, uint64_t seed, double* gram, double* R,
                    int* flags, int* any_flag, int* skipped);
 
+/* What one n2v2r_gram_apply launched, from the solver's own plan of that application. */
+typedef struct n2v2r_gram_info {
+  int form;       /* as n2v2r_eig_stats.spmm_form: 0 flat sum, 1 XCD-split, 4 dense, 5 tiled */
+  int rs_form;    /* 1: stage 2 as the reduce-scatter of the rank's column share */
+  int rs_chunks;  /* ... in this many row chunks (1: one launch; 0 without rs_form) */
+  int split2;     /* 1: both stages split over the XCDs, W summed from per-layer partials */
+  int tile_nb, tile_wb, tile_rows; /* tiled form: column blocks, window bits, rows per tile (else 0) */
+  int rpw1, rpw2; /* rows per wave of the last row-kernel launch of stage 1 / stage 2 (the
+                     launcher's rule on the arguments launched); 0: that stage ran no row kernel */
+} n2v2r_gram_info;
+
+/* One application W = M X = sum_k A_k (A_k^T X) at panel width b (8, 16, 32 or 64) alone (tests),
+ * through the solver's own set-up steps and launches: whichever form a fit at this width would
+ * take on this handle under the environment switches in force (flat, XCD-split, tiled, dense;
+ * on a rank handle the gather or the reduce-scatter form).  X: the global N x b panel (a rank
+ * handle uploads its own rows and gathers the rest from its peers: the call is collective, every
+ * rank makes it with the same X).  W: this handle's n_local x b rows of M X.  Z (optional):
+ * K x n_local x b, the stage-1 panels Z_k = A_k^T X.  Every row the application has to write --
+ * W, the Z_k, the split form's partials, a rank handle's gathered panels -- is filled with NaN
+ * bytes first, so a row no launch wrote shows in the result.  info (optional): what ran.  The
+ * handle's embedding and ranking results are left alone, and a later fit is bit-identical to one
+ * without the call.  N2V2R_ERR_BAD_ARG for another b, for missing layers and on a multi-GPU
+ * parent handle (its ranks would each need the call). */
+int n2v2r_gram_apply(n2v2r_handle* h, int b, const float* X, float* Z, float* W,
+                     n2v2r_gram_info* info);
+
 /* Banded Rayleigh-Ritz stage alone (tests; block width 8, c <= 512, kp + 8 <= 192): the
  * projected matrix of a Krylov-Schur cycle given as UASE keeps it.  Basis order [X (kp
  * columns, diagonal theta_prev), E, Z_2, ...] in 8-wide blocks; hband holds band column

@@ -53,6 +53,7 @@ EXPORTED = [
     "n2v2r_create_multi", "n2v2r_multi_devices", "n2v2r_h2d_layer_bytes",
     "n2v2r_set_layer_corr", "n2v2r_get_layer_dense", "n2v2r_transform_layer",
     "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles", "n2v2r_pip_pass",
+    "n2v2r_gram_apply",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -88,6 +89,11 @@ class EigStats(ctypes.Structure):
             v = getattr(self, k)
             out[k] = list(v) if isinstance(v, ctypes.Array) else v
         return out
+
+
+class GramInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("form", "rs_form", "rs_chunks", "split2", "tile_nb",
+                                            "tile_wb", "tile_rows", "rpw1", "rpw2")]
 
 
 class TransformStats(ctypes.Structure):
@@ -162,6 +168,8 @@ def load(path: str | None = None):
             "n2v2r_pip_pass": (_i, [_vp, _i64, _i, _p(np.float32), _p(np.float32), _vp,
                                     ctypes.c_float, _i, _i, ctypes.c_uint64, _p(np.float64), _vp,
                                     _p(np.int32), _p(np.int32), _p(np.int32)]),
+            "n2v2r_gram_apply": (_i, [_vp, _i, _p(np.float32), _vp, _p(np.float32),
+                                      ctypes.POINTER(GramInfo)]),
             "n2v2r_rr_band_top": (_i, [_vp, _i, _i, _p(np.float64), ctypes.c_int64, _vp, _i,
                                        _p(np.float64), _p(np.float32)]),
             "n2v2r_set_layer_dense": (_i, [_vp, _i, _i64, _p(np.float32), _i]),
@@ -730,6 +738,24 @@ class Engine:
             "pip_pass")
         return {"Za": za, "Zb": zb, "gram": gram, "R": R, "flags": flags,
                 "any_flag": int(any_flag[0]), "skipped": skipped}
+
+    def gram_apply(self, X, want_z: bool = True):
+        """One application W = sum_k A_k (A_k^T X) through the solver's own launches (see
+        n2v2r_gram_apply).  X: the global (N, b) fp32 panel, b = 8, 16, 32 or 64; on a rank handle
+        every rank calls with the same X.  Returns (W, Z, info): this handle's (n_local, b) rows
+        of M X, the stage-1 panels (K, n_local, b) (None without want_z) and a dict naming the form
+        that ran (the fields of n2v2r_gram_info)."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[0] != self.n:
+            raise ValueError(f"gram_apply: X must be ({self.n}, b), got {X.shape}")
+        b, nl = X.shape[1], self._n_local()
+        W = np.empty((nl, b), dtype=np.float32)
+        Z = np.empty((self.num_layers, nl, b), dtype=np.float32) if want_z else None
+        info = GramInfo()
+        self._check(self.lib.n2v2r_gram_apply(
+            self.h, int(b), X, Z.ctypes.data_as(ctypes.c_void_p) if want_z else None, W,
+            ctypes.byref(info)), "gram_apply")
+        return W, Z, {k: getattr(info, k) for k, _ in GramInfo._fields_}
 
     def rr_band_top(self, hband, c: int, kp: int, theta_prev, p: int):
         """Banded Rayleigh-Ritz stage alone (see n2v2r_rr_band_top).  Returns (w, S)."""

@@ -239,6 +239,8 @@ struct Eig {
   // (the local first pass of the next expansion), or by materialize() before any other use
   bool split2 = false;
   float* pending = nullptr;  // the W block whose value still sits in the partials
+  // rows per wave of the last row-kernel launch of stage 1 / stage 2 (0: none yet; diagnostics)
+  int rpw1 = 0, rpw2 = 0;
   int stats_rr_fallbacks = 0;  // Sturm Rayleigh-Ritz cycles redone by the reducing path
   // dense Rayleigh-Ritz: the multi-workgroup tridiagonalisation's error word of the current
   // cycle (nullptr: the one-workgroup kernel ran), and whether a timeout switched the fit to the
@@ -512,6 +514,7 @@ struct Eig {
         a.X[i] = xg;
         a.Y[i] = zk(k0 + i);
       }
+      a.rpw = rpw1 = n2v2r_spmm_rpw(a, b);  // (the launcher's own choice, kept for n2v2r_gram_apply)
       te = tbeg();
       HIPCHK(n2v2r_launch_spmm(a, b, st));
     }
@@ -554,6 +557,7 @@ struct Eig {
       for (int k = 0; k < K; ++k) s.Y[k] = s2part(k);
       pending = Wout;
     }
+    s.rpw = rpw2 = n2v2r_spmm_rpw(s, b);
     const double bytes = stage_bytes(false);
     const int te = tbeg();
     HIPCHK(n2v2r_launch_spmm(s, b, st));
@@ -609,6 +613,8 @@ struct Eig {
       b1 += spmm_algo_bytes(L.c_nnz, s2.A[k].unit != 0, ng, npad, b);
     }
     s2.Y[0] = P;
+    // the whole share's choice, for every chunk: each row is summed as in one launch
+    s2.rpw = rpw2 = n2v2r_spmm_rpw(s2, b);
     const int te = tbeg();
     if (rs_chunks <= 1) {
       HIPCHK(n2v2r_launch_spmm(s2, b, st));
@@ -620,7 +626,6 @@ struct Eig {
       // scattered on the collective stream while chunk c + 1's product runs.  Every row is
       // summed as in the one-launch form (same rows per wave), and every element of W sums the
       // same ranks' values: the same result, with one chunk's reduce-scatter exposed.
-      s2.rpw = n2v2r_spmm_rpw(s2, b);
       const int W = h->world;
       for (int c = 0; c < rs_chunks; ++c) {
         const int64_t r0 = (int64_t)c * rs_rc;
@@ -1528,6 +1533,9 @@ struct Eig {
     kry0 = pb;
   }
 
+  // the application's form as n2v2r_eig_stats.spmm_form codes it
+  int spmm_form() const { return h->dense_layers() ? 4 : col_blocks ? 5 : split2 ? 1 : 0; }
+
   void fill_stats() {
     if (!stats) return;
     stats->restarts = cycle + 1;
@@ -1546,7 +1554,7 @@ struct Eig {
     stats->est_scale = est_scale;
     stats->lean_checks = lean_checks;
     stats->pool_blocks = (int)h->ews.pool.size();
-    stats->spmm_form = h->dense_layers() ? 4 : col_blocks ? 5 : split2 ? 1 : 0;
+    stats->spmm_form = spmm_form();
     stats->stag_cap = stag_cap;
     stats->y_captured = y_captured ? 1 : 0;
     stats->tri_fallbacks = tri_fallbacks;
@@ -1916,6 +1924,72 @@ int n2v2r_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_sta
                  stats ? stats->max_residual : -1.0, o.tol > 0 ? o.tol : 1e-6,
                  stats && stats->stagnated ? "; stopped flat above the fp32-floor cap" : "");
     return st;
+  });
+}
+
+// One application of M alone (tests): an Eig set up as a fit's, its apply_M on a host panel.
+int n2v2r_gram_apply(n2v2r_handle* h, int b, const float* X, float* Z, float* W,
+                     n2v2r_gram_info* info) {
+  return guarded(h, [&]() -> int {
+    if (h->multi() || (b != 8 && b != 16 && b != 32 && b != 64) || !X || !W) return N2V2R_ERR_BAD_ARG;
+    if (h->K < 1) {
+      h->err = "no layers set";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    for (auto& L : h->layers)
+      if (!L->loaded) {
+        h->err = "a layer was not loaded";
+        return N2V2R_ERR_BAD_ARG;
+      }
+    Eig eig{};
+    eig.h = h;
+    eig.st = h->stream;
+    eig.n = h->nloc;
+    eig.npad = h->npad;
+    eig.row0 = h->row0;
+    eig.K = h->K;
+    eig.b = b;
+    eig.stats = nullptr;
+    eig.reuse_pool();
+    eig.setup_tiled_spmm();
+    eig.setup_stage2_form();
+    hipStream_t st = eig.st;
+    float* x = eig.take();
+    float* w = eig.take();
+    // NaN bytes wherever the application has to write: the local rows of W, of every Z_k and of
+    // the split form's partials (padding rows stay the zeros the solver keeps there), and a rank's
+    // gathered panels whole (the collectives write all of them, or all that is read)
+    const size_t rows = sizeof(float) * (size_t)eig.n * b;
+    HIPCHK(hipMemsetAsync(w, 0xFF, rows, st));
+    for (int k = 0; k < eig.K; ++k) HIPCHK(hipMemsetAsync(eig.zk(k), 0xFF, rows, st));
+    if (eig.split2)
+      for (int k = 0; k < eig.K; ++k) HIPCHK(hipMemsetAsync(eig.s2part(k), 0xFF, rows, st));
+    if (h->comm) {
+      HIPCHK(hipMemsetAsync(h->gath.p, 0xFF, h->gath.bytes, st));
+      HIPCHK(hipMemsetAsync(h->ews.zg.p, 0xFF, h->ews.zg.bytes, st));
+    }
+    HIPCHK(hipMemcpyAsync(x, X + (size_t)eig.row0 * b, rows, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // pageable source: complete before the kernels
+    eig.apply_M(x, w);
+    eig.materialize();
+    HIPCHK(hipMemcpyAsync(W, w, rows, hipMemcpyDeviceToHost, st));
+    if (Z)
+      for (int k = 0; k < eig.K; ++k)
+        HIPCHK(hipMemcpyAsync(Z + (size_t)k * eig.n * b, eig.zk(k), rows, hipMemcpyDeviceToHost,
+                              st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (info) {
+      info->form = eig.spmm_form();
+      info->rs_form = eig.rs_form ? 1 : 0;
+      info->rs_chunks = eig.rs_form ? eig.rs_chunks : 0;
+      info->split2 = eig.split2 ? 1 : 0;
+      info->tile_nb = eig.col_blocks ? eig.tile_nb : 0;
+      info->tile_wb = eig.col_blocks ? eig.tile_wb : 0;
+      info->tile_rows = eig.col_blocks ? eig.tile_rows : 0;
+      info->rpw1 = eig.rpw1;
+      info->rpw2 = eig.rpw2;
+    }
+    return N2V2R_OK;
   });
 }
 
