@@ -271,6 +271,39 @@ int n2v2r_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
  * diagonal included -- the message names the count of either. */
 enum { N2V2R_TOM_UNSIGNED = 0, N2V2R_TOM_SIGNED = 1 };
 int n2v2r_tom_layer(n2v2r_handle* h, int k, int type);
+/* Every loaded layer of a DENSE-storage handle becomes a CSR-storage layer, in HBM: the way from
+ * a layer the GPU built and sparsified (n2v2r_set_layer_corr, n2v2r_tom_layer,
+ * n2v2r_transform_layer; n2v2r_set_layer_dense layers as well) to the sparse fit, without a
+ * visit to the host.  All layers convert at once (the "all CSR or all dense" rule).
+ * An entry is stored when a != 0 and its column is < n: -0 is zero and dropped, a NaN is non-zero
+ * and kept, as scipy.sparse.csr_matrix(dense) does; columns ascend in every row.  Per matrix one
+ * count pass, an exclusive scan of the row counts and one compaction pass read the layer (two
+ * reads of 4 n^2 bytes); no atomics order the output, which is a function of the layer alone.
+ * After the call every layer is in the state n2v2r_set_layer_csr would have left for the same
+ * matrix (on a rank handle: n2v2r_set_layer_csr_rows, with the rank's rows of A^T as well for a
+ * directed layer, compacted from the layer's dense A^T copy: no sort, so the 2^31 - 1 entry limit
+ * of the GPU transpose does not apply): local rows, global int32 columns, int64 row pointers;
+ * `symmetric` is carried over; a layer whose stored values are all 1.0f counts as unweighted (its
+ * value array is a 1.0f fill that the SpMM does not read).  The dense copies, the column-block
+ * forms and the scratch of n2v2r_tom_layer are released and the embedding is cleared;
+ * n2v2r_uase, n2v2r_column_sums and the diagnostics then behave as on a handle whose layers came
+ * in through n2v2r_set_layer_csr.
+ * nnz (optional): K counts of stored entries of A_k, over all ranks.
+ * Memory: the dense layers and all CSR buffers exist together at the peak, 8 B per stored entry
+ * (4 B column + 4 B value; unweighted layers keep the value fill) and 8 B per row on top of the
+ * 4 n^2 B per layer (twice both for a directed layer); afterwards only the CSR remains.
+ * Atomic: the counts and every allocation for every layer come first, then the compaction; the
+ * layers change only after every kernel has succeeded.  A refused or failed call
+ * (N2V2R_ERR_OUT_OF_MEMORY included) leaves the handle as it was, and the dense fit still runs.
+ * On a partitioned handle the call is collective: every rank converts its own rows (no layer data
+ * moves between ranks), the counts are summed and the status reduced over the ranks before
+ * anyone commits, so all ranks convert or none and all return the same status.
+ * N2V2R_ERR_BAD_ARG, nothing changed: no layers set; a layer of the handle not loaded; a handle
+ * whose layers are already CSR. */
+int n2v2r_layers_to_csr(n2v2r_handle* h, int64_t* nnz /* K global counts, may be NULL */);
+/* The count pass of n2v2r_layers_to_csr alone: nnz[k] = the stored entries (a != 0, column < n)
+ * of the dense-storage layer k over all ranks.  Nothing changes; the same refusals. */
+int n2v2r_count_layer_nonzeros(n2v2r_handle* h, int64_t* nnz /* K global counts */);
 /* distributed ingest without the global CSR on every rank: the caller's own rows
  * [row0, row0 + n_rows) (must equal n2v2r_dist_info's) of a SYMMETRIC layer, indptr local
  * (starting at 0), column indices global. */

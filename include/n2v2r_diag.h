@@ -105,6 +105,27 @@ int n2v2r_h2d_layer_bytes(const n2v2r_handle* h, int64_t* per_rank, int cap);
  * N2V2R_ERR_BAD_ARG when layer k is not a loaded dense layer. */
 int n2v2r_get_layer_dense(n2v2r_handle* h, int k, float* A /* n x n */);
 
+/* A loaded CSR layer's local rows copied back to the host (layers that came in through
+ * n2v2r_set_layer_csr / _rows or n2v2r_layers_to_csr): the thresholded network as an edge
+ * structure, without an n x n host array.  transpose = 1 reads the A^T copy of a directed layer
+ * (N2V2R_ERR_BAD_ARG for a symmetric one, which keeps none).  n2v2r_get_layer_csr_nnz gives the
+ * entry count to size the buffers with.  indptr: n_local + 1 row pointers starting at 0; indices:
+ * global columns; data: the values, 1.0f for an unweighted layer.  A rank handle returns its
+ * n_local rows, a multi-GPU handle all N rows (the ranks' rows one after the other).
+ * N2V2R_ERR_BAD_ARG when layer k is not a loaded CSR layer. */
+int n2v2r_get_layer_csr_nnz(n2v2r_handle* h, int k, int transpose, int64_t* nnz);
+int n2v2r_get_layer_csr(n2v2r_handle* h, int k, int transpose, int64_t* indptr, int32_t* indices,
+                        float* data);
+
+/* One kernel of n2v2r_layers_to_csr alone on the loaded dense layer k of a one-GPU handle
+ * (tools/sparsify_probe.py): which = 0 dense_row_count_kernel, 1 dense_row_compact_kernel (into
+ * scratch buffers; the layer stays dense), timed with one HIP event pair on the engine stream
+ * around `reps` launches back to back after one warm-up.  avg_ms = the span / reps; bytes = the
+ * layer bytes one launch reads (the compaction writes 8 B per stored entry besides, 4 B for an
+ * unweighted layer). */
+int n2v2r_bench_sparsify_pass(n2v2r_handle* h, int k, int which, int reps, double* avg_ms,
+                              double* bytes);
+
 /* One kernel of n2v2r_transform_layer alone on the loaded dense layer k of a one-GPU handle, timed
  * with one HIP event pair on the engine stream around `reps` launches back to back, after one
  * warm-up (the roofline of tools/layer_transform_probe.py).  which: 0..3 the radix-select

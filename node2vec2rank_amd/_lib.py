@@ -53,7 +53,8 @@ EXPORTED = [
     "n2v2r_create_multi", "n2v2r_multi_devices", "n2v2r_h2d_layer_bytes",
     "n2v2r_set_layer_corr", "n2v2r_get_layer_dense", "n2v2r_transform_layer",
     "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles", "n2v2r_pip_pass",
-    "n2v2r_gram_apply",
+    "n2v2r_gram_apply", "n2v2r_layers_to_csr", "n2v2r_count_layer_nonzeros",
+    "n2v2r_get_layer_csr_nnz", "n2v2r_get_layer_csr", "n2v2r_bench_sparsify_pass",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -197,6 +198,13 @@ def load(path: str | None = None):
             "n2v2r_tom_layer": (_i, [_vp, _i, _i]),
             "n2v2r_bench_tom_tiles": (_i, [_vp, _i, _i, _i, _p(np.float64),
                                            ctypes.POINTER(ctypes.c_double)]),
+            "n2v2r_layers_to_csr": (_i, [_vp, _vp]),
+            "n2v2r_count_layer_nonzeros": (_i, [_vp, _p(np.int64)]),
+            "n2v2r_get_layer_csr_nnz": (_i, [_vp, _i, _i, ctypes.POINTER(_i64)]),
+            "n2v2r_get_layer_csr": (_i, [_vp, _i, _i, _p(np.int64), _p(np.int32),
+                                         _p(np.float32)]),
+            "n2v2r_bench_sparsify_pass": (_i, [_vp, _i, _i, _i, ctypes.POINTER(ctypes.c_double),
+                                               ctypes.POINTER(ctypes.c_double)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -369,15 +377,36 @@ class Engine:
         raise RuntimeError(msg)
 
     # -- layers ----------------------------------------------------------------------------
-    def set_layers(self, layers, symmetric=SYM_DETECT, storage="auto"):
+    def set_layers(self, layers, symmetric=SYM_DETECT, storage="auto", sparsify=False):
         """layers: list of scipy.sparse matrices (any format) or dense arrays, N x N, or
         ``Coexpression`` layers (an N x samples expression matrix each: the engine builds the
         N x N co-expression layer on the GPU, n2v2r_set_layer_corr).
 
         storage: "csr", "dense" (fp32 N x N in HBM, MFMA GEMMs) or "auto" (dense when every
         layer is a dense array with more than 1/4 of its entries non-zero).  A list that holds a
-        ``Coexpression`` is dense storage: its other layers must be dense arrays."""
+        ``Coexpression`` is dense storage: its other layers must be dense arrays.
+
+        sparsify: what becomes of dense-storage layers once the last one is built and
+        transformed.  ``False``: they stay dense.  ``True``: ``to_csr()``, the conversion to CSR
+        in HBM (the sparse fit of a thresholded network).  ``"auto"``: ``to_csr()`` when every
+        layer ends at most 1/4 non-zero, counted on the GPU (the rule ``storage="auto"`` applies
+        to host arrays; with ``sparsify`` set, dense arrays under ``storage="auto"`` are loaded
+        dense and counted there, never scanned on the host).  ``ValueError`` with
+        ``storage="csr"`` or sparse inputs: there is nothing to convert."""
         import scipy.sparse as sp
+        if not (sparsify is False or sparsify is True or
+                (isinstance(sparsify, str) and sparsify == "auto")):
+            raise ValueError(f"sparsify must be False, True or 'auto', got {sparsify!r}")
+        if sparsify is not False:
+            # (as every refusal of this method: before the first library call)
+            if any(sp.issparse(a) for a in layers):
+                raise ValueError("sparsify converts dense-storage layers: a sparse layer is "
+                                 "stored as CSR already, there is nothing to convert")
+            if storage == "csr":
+                raise ValueError("sparsify converts dense-storage layers: with storage='csr' "
+                                 "there is nothing to convert")
+            if storage == "auto":
+                storage = "dense"
         corr = [isinstance(a, Coexpression) for a in layers]
         if any(corr):
             # (every check before the first library call: a refused list leaves the handle as is)
@@ -413,6 +442,7 @@ class Engine:
             self.n = n
             self.num_layers = len(arrs)
             self.storage = "dense"
+            self._sparsify(sparsify)
             return
         if storage == "auto":
             storage = "csr"
@@ -434,6 +464,7 @@ class Engine:
             self.n = n
             self.num_layers = len(arrs)
             self.storage = "dense"
+            self._sparsify(sparsify)
             return
         mats = [sp.csr_matrix(a, dtype=np.float32) for a in layers]
         n = mats[0].shape[0]
@@ -603,6 +634,59 @@ class Engine:
         A = np.zeros((self.n, self.n), dtype=np.float32)
         self._check(self.lib.n2v2r_get_layer_dense(self.h, int(k), A), "layer_dense")
         return A
+
+    def _sparsify(self, sparsify):
+        """The ``sparsify`` option of ``set_layers`` on the dense-storage layers just loaded."""
+        if sparsify is False:
+            return
+        if sparsify == "auto" and any(4 * c > self.n * self.n for c in self.count_nonzeros()):
+            return
+        self.to_csr()
+
+    def count_nonzeros(self) -> list:
+        """Stored entries (non-zero, a NaN included, -0 not) of every dense-storage layer, counted
+        on the GPU over all ranks (n2v2r_count_layer_nonzeros); nothing changes."""
+        out = np.zeros(max(int(getattr(self, "num_layers", 0)), 8), dtype=np.int64)
+        self._check(self.lib.n2v2r_count_layer_nonzeros(self.h, out), "count_nonzeros")
+        return [int(x) for x in out[:self.num_layers]]
+
+    def to_csr(self) -> list:
+        """Every dense-storage layer of the handle to CSR storage, in HBM (n2v2r_layers_to_csr):
+        afterwards the handle is what ``set_layers`` with the same matrices as scipy CSR would
+        have left, the fit is the sparse one and ``storage == "csr"``.  Returns the stored entries
+        per layer (over all ranks).  ``ValueError`` (handle untouched): no layers, a layer not
+        loaded, layers that are CSR already; ``MemoryError`` leaves the dense layers in place too."""
+        out = np.zeros(max(int(getattr(self, "num_layers", 0)), 8), dtype=np.int64)
+        self._check(self.lib.n2v2r_layers_to_csr(self.h, out.ctypes.data_as(ctypes.c_void_p)),
+                    "to_csr")
+        self.storage = "csr"
+        return [int(x) for x in out[:self.num_layers]]
+
+    def layer_csr(self, k: int, transpose: bool = False):
+        """CSR layer k back on the host as a ``scipy.sparse.csr_matrix`` of shape (n_local, n)
+        (n2v2r_get_layer_csr): this handle's rows, global columns; all N rows on a multi-GPU
+        handle.  ``transpose=True``: the A^T copy of a directed layer (``ValueError`` for a
+        symmetric one)."""
+        import scipy.sparse as sp
+        nnz = _i64()
+        self._check(self.lib.n2v2r_get_layer_csr_nnz(self.h, int(k), int(bool(transpose)),
+                                                     ctypes.byref(nnz)), "layer_csr")
+        nl, m = self._n_local(), int(nnz.value)
+        indptr = np.zeros(nl + 1, dtype=np.int64)
+        indices = np.zeros(max(m, 1), dtype=np.int32)
+        data = np.zeros(max(m, 1), dtype=np.float32)
+        self._check(self.lib.n2v2r_get_layer_csr(self.h, int(k), int(bool(transpose)), indptr,
+                                                 indices, data), "layer_csr")
+        return sp.csr_matrix((data[:m], indices[:m], indptr), shape=(nl, self.n))
+
+    def bench_sparsify_pass(self, k: int, which: int, reps: int = 20):
+        """Time one kernel of ``to_csr`` alone on dense layer k (n2v2r_bench_sparsify_pass):
+        ``which`` 0 the count pass, 1 the compaction.  Returns (ms, layer bytes read)."""
+        ms, by = ctypes.c_double(), ctypes.c_double()
+        self._check(self.lib.n2v2r_bench_sparsify_pass(self.h, int(k), int(which), int(reps),
+                                                       ctypes.byref(ms), ctypes.byref(by)),
+                    "bench_sparsify_pass")
+        return ms.value, by.value
 
     def transform_layer(self, k: int, threshold=None, top_percent_keep=100, binarize=False,
                         absolute=False) -> dict:

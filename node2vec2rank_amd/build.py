@@ -18,7 +18,7 @@ _TAG = os.environ.get("N2V2R_BUILD_TAG", "")
 LIB = os.path.join(OUT_DIR, f"libn2v2r_hip_{_TAG}.so" if _TAG else "libn2v2r_hip.so")
 OBJ_DIR = os.path.join(OUT_DIR, f"obj_{_TAG}" if _TAG else "obj")
 
-HIP_SOURCES = ["spmm.hip", "dense.hip", "gemm.hip", "corr.hip", "tom.hip", "transform.hip", "rank.hip",
+HIP_SOURCES = ["spmm.hip", "dense.hip", "gemm.hip", "corr.hip", "tom.hip", "transform.hip", "sparsify.hip", "rank.hip",
                "rr.hip", "rr_band.hip", "rr_sturm.hip", "ingest.hip", "engine.cpp", "layers.cpp",
                "comm.cpp", "solver.cpp", "ranking.cpp", "multi.cpp"]
 HOST_SOURCES: list = []

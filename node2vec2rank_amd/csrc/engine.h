@@ -141,6 +141,14 @@ hipError_t n2v2r_launch_tf_min(const float* A, int64_t count, int absolute, floa
                                uint32_t xkey, unsigned long long* out, hipStream_t stream);
 hipError_t n2v2r_launch_tf_apply(float* A, int64_t count, int absolute, float lim, int binarize,
                                  unsigned long long* kept, hipStream_t stream);
+// sparsify.hip: a dense layer's rows to CSR (stored: a != 0 and column < n)
+hipError_t n2v2r_launch_dense_row_count(const float* A, int64_t n_rows, int64_t lda, int64_t n,
+                                        int64_t* counts, unsigned* flag, hipStream_t stream);
+hipError_t n2v2r_launch_row_scan(const int64_t* counts, int64_t n_rows, int64_t* indptr,
+                                 hipStream_t stream);
+hipError_t n2v2r_launch_dense_row_compact(const float* A, int64_t n_rows, int64_t lda, int64_t n,
+                                          const int64_t* indptr, int32_t* idx, float* val,
+                                          hipStream_t stream);
 hipError_t n2v2r_launch_transpose(const float* in, int64_t ldi, int64_t rows, int64_t cols,
                                   float* out, int64_t ldo, hipStream_t stream);
 hipError_t n2v2r_launch_mismatch(const float* a, const float* b, int64_t ld, int64_t rows,
@@ -758,6 +766,11 @@ int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, con
 int multi_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
                           double top_percent_keep, n2v2r_transform_stats* stats);
 int multi_tom_layer(n2v2r_handle* h, int k, int type);
+int multi_layers_to_csr(n2v2r_handle* h, int64_t* nnz);
+int multi_count_layer_nonzeros(n2v2r_handle* h, int64_t* nnz);
+int multi_get_layer_csr_nnz(n2v2r_handle* h, int k, int transpose, int64_t* nnz);
+int multi_get_layer_csr(n2v2r_handle* h, int k, int transpose, int64_t* indptr, int32_t* indices,
+                        float* data);
 int multi_get_layer_dense(n2v2r_handle* h, int k, float* A);
 int multi_column_sums(n2v2r_handle* h, int k, float* out);
 int multi_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_stats* stats);

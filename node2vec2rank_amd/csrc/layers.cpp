@@ -881,6 +881,300 @@ int n2v2r_tom_layer(n2v2r_handle* h, int k, int type) {
   });
 }
 
+}  // extern "C"
+
+namespace {
+// one matrix of a layer (its dA or dAT rows) on its way to CSR
+struct CsrBuild {
+  DevBuf ip, ix, dv;
+  int64_t nnz = 0;
+  bool unit = true;
+};
+
+// row pointers of the stored entries of the handle's rows of A (nloc x lda): b.ip, b.nnz, b.unit.
+// cnt: scratch of the per-row counts
+void sparsify_count(n2v2r_handle* h, const float* A, int64_t lda, DevBuf& cnt, CsrBuild& b) {
+  hipStream_t st = h->stream;
+  const int64_t nr = h->nloc;
+  cnt.ensure_raw(sizeof(int64_t) * std::max<int64_t>(nr, 1));
+  b.ip.ensure_raw(sizeof(int64_t) * (nr + 1));
+  h->ing_flag.ensure_raw(sizeof(unsigned) * 4);
+  unsigned* flag = h->ing_flag.as<unsigned>();
+  HIPCHK(hipMemsetAsync(flag, 0, sizeof(unsigned), st));
+  HIPCHK(n2v2r_launch_dense_row_count(A, nr, lda, h->n, cnt.as<int64_t>(), flag, st));
+  HIPCHK(n2v2r_launch_row_scan(cnt.as<int64_t>(), nr, b.ip.as<int64_t>(), st));
+  unsigned fl = 0;
+  int64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&fl, flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&total, b.ip.as<int64_t>() + nr, sizeof(int64_t), hipMemcpyDeviceToHost,
+                        st));
+  HIPCHK(hipStreamSynchronize(st));
+  b.nnz = total;
+  b.unit = !(fl & 1u);
+}
+
+// the refusals n2v2r_layers_to_csr and n2v2r_count_layer_nonzeros share (nothing changed)
+int sparsify_refusal(n2v2r_handle* h, const char* what) {
+  if (h->K < 1 || h->layers.empty()) {
+    h->set_err("%s: no layers set", what);
+    return N2V2R_ERR_BAD_ARG;
+  }
+  for (int k = 0; k < h->K; ++k)
+    if (!h->layers[k]->loaded) {
+      h->set_err("%s: layer %d is not loaded", what, k);
+      return N2V2R_ERR_BAD_ARG;
+    }
+  if (!h->layers[0]->dense) {
+    h->set_err("%s: the layers of this handle are already CSR", what);
+    return N2V2R_ERR_BAD_ARG;
+  }
+  return N2V2R_OK;
+}
+
+// the loaded CSR layer k's A (or A^T) rows for the read-back; nullptr with the error set
+const LayerDev* csr_layer_for_read(n2v2r_handle* h, int k, int transpose) {
+  if (k < 0 || k >= h->K || !h->layers[k]->loaded || h->layers[k]->dense) {
+    h->set_err("get_layer_csr: layer %d is not a loaded CSR layer", k);
+    return nullptr;
+  }
+  if (transpose && h->layers[k]->symmetric) {
+    h->set_err("get_layer_csr: layer %d is symmetric: it keeps no A^T copy", k);
+    return nullptr;
+  }
+  return h->layers[k].get();
+}
+}  // namespace
+
+extern "C" {
+
+// Every dense layer to CSR in HBM (sparsify.hip).  Counts first, then every allocation, then the
+// compaction kernels, all into buffers of this call; the layers change only after every kernel
+// has succeeded on every rank (the failure status is reduced over the ranks before the commit),
+// so a refused or failed call leaves the dense layers as they were.
+int n2v2r_layers_to_csr(n2v2r_handle* h, int64_t* nnz) {
+  if (h && h->multi()) return multi_layers_to_csr(h, nnz);
+  return guarded(h, [&]() -> int {
+    if (const int st = sparsify_refusal(h, "layers_to_csr")) return st;
+    const int K = h->K;
+    hipStream_t st = h->stream;
+    DevBuf red;  // [0, K) this rank's counts, [K] its status
+    if (h->comm) red.ensure_raw(sizeof(unsigned long long) * (K + 1));
+    std::vector<CsrBuild> a(K), t(K);
+    int fail = N2V2R_OK;
+    std::string why;
+    try {
+      DevBuf cnt;
+      for (int k = 0; k < K; ++k) {
+        const LayerDev& L = *h->layers[k];
+        sparsify_count(h, L.dA.as<float>(), L.lda, cnt, a[k]);
+        if (!L.symmetric) sparsify_count(h, L.dAT.as<float>(), L.lda, cnt, t[k]);
+      }
+      for (int k = 0; k < K; ++k)
+        for (CsrBuild* b : {&a[k], &t[k]}) {
+          if (b == &t[k] && h->layers[k]->symmetric) continue;
+          b->ix.ensure_raw(sizeof(int32_t) * std::max<int64_t>(b->nnz, 1));
+          b->dv.ensure_raw(sizeof(float) * std::max<int64_t>(b->nnz, 1));
+        }
+      for (int k = 0; k < K; ++k) {
+        const LayerDev& L = *h->layers[k];
+        for (CsrBuild* b : {&a[k], &t[k]}) {
+          const bool tr = b == &t[k];
+          if (tr && L.symmetric) continue;
+          if (b->unit && b->nnz)  // (0x3F800000 = 1.0f: the values of an unweighted layer)
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b->dv.p, 0x3F800000, (size_t)b->nnz, st));
+          HIPCHK(n2v2r_launch_dense_row_compact((tr ? L.dAT : L.dA).as<float>(), h->nloc, L.lda,
+                                                h->n, b->ip.as<int64_t>(), b->ix.as<int32_t>(),
+                                                b->unit ? nullptr : b->dv.as<float>(), st));
+        }
+      }
+      HIPCHK(hipStreamSynchronize(st));
+    } catch (const StatusFail& sf) {
+      fail = sf.code;
+      why = sf.msg;
+      (void)hipGetLastError();
+    } catch (const HipFail& hf) {
+      fail = N2V2R_ERR_HIP;
+      why = std::string("HIP error (") + hipGetErrorString(hf.e) + ") at " + hf.where;
+      (void)hipGetLastError();
+    }
+    std::vector<unsigned long long> tot(K + 1);
+    for (int k = 0; k < K; ++k) tot[k] = fail ? 0ull : (unsigned long long)a[k].nnz;
+    tot[K] = (unsigned long long)fail;
+    if (h->comm) {  // the global counts, and one status for every rank
+      unsigned long long* r = red.as<unsigned long long>();
+      HIPCHK(hipMemcpyAsync(r, tot.data(), sizeof(unsigned long long) * (K + 1),
+                            hipMemcpyHostToDevice, st));
+      h->comm->allreduce_sum_u64(r, K, st);
+      h->comm->allreduce_max_u64(r + K, 1, st);
+      HIPCHK(hipMemcpyAsync(tot.data(), r, sizeof(unsigned long long) * (K + 1),
+                            hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    if (tot[K] != N2V2R_OK) {
+      if (fail)
+        h->err = "layers_to_csr: " + why;
+      else
+        h->set_err("layers_to_csr: another rank failed (status %d); nothing was converted",
+                   (int)tot[K]);
+      return fail ? fail : (int)tot[K];
+    }
+    for (int k = 0; k < K; ++k) {
+      LayerDev& L = *h->layers[k];
+      L.drop_col_blocks();
+      L.indptr.swap(a[k].ip);
+      L.indices.swap(a[k].ix);
+      L.data.swap(a[k].dv);
+      L.nnz = a[k].nnz;
+      L.unit = a[k].unit;
+      if (L.symmetric) {
+        L.t_indptr.release();
+        L.t_indices.release();
+        L.t_data.release();
+        L.t_nnz = L.nnz;
+        L.t_unit = L.unit;
+      } else {
+        L.t_indptr.swap(t[k].ip);
+        L.t_indices.swap(t[k].ix);
+        L.t_data.swap(t[k].dv);
+        L.t_nnz = t[k].nnz;
+        L.t_unit = t[k].unit;
+      }
+      L.n_rows = h->nloc;
+      L.dense = false;
+      L.dA.release();
+      L.dAT.release();
+      if (nnz) nnz[k] = (int64_t)tot[k];
+    }
+    h->tom_out.release();
+    h->dense_work.release();
+    h->dense_work_elems = 0;
+    h->have_embedding = false;
+    return N2V2R_OK;
+  });
+}
+
+// the count pass of n2v2r_layers_to_csr alone: nothing changes
+int n2v2r_count_layer_nonzeros(n2v2r_handle* h, int64_t* nnz) {
+  if (h && h->multi()) return multi_count_layer_nonzeros(h, nnz);
+  return guarded(h, [&]() -> int {
+    if (!nnz) {
+      h->err = "count_layer_nonzeros: null output buffer";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (const int st = sparsify_refusal(h, "count_layer_nonzeros")) return st;
+    const int K = h->K;
+    hipStream_t st = h->stream;
+    std::vector<unsigned long long> tot(K);
+    DevBuf cnt;
+    for (int k = 0; k < K; ++k) {
+      CsrBuild b;
+      sparsify_count(h, h->layers[k]->dA.as<float>(), h->layers[k]->lda, cnt, b);
+      tot[k] = (unsigned long long)b.nnz;
+    }
+    if (h->comm) {
+      DevBuf red;
+      red.ensure_raw(sizeof(unsigned long long) * K);
+      unsigned long long* r = red.as<unsigned long long>();
+      HIPCHK(hipMemcpyAsync(r, tot.data(), sizeof(unsigned long long) * K, hipMemcpyHostToDevice,
+                            st));
+      h->comm->allreduce_sum_u64(r, K, st);
+      HIPCHK(hipMemcpyAsync(tot.data(), r, sizeof(unsigned long long) * K, hipMemcpyDeviceToHost,
+                            st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    for (int k = 0; k < K; ++k) nnz[k] = (int64_t)tot[k];
+    return N2V2R_OK;
+  });
+}
+
+// diagnostics (n2v2r_diag.h): a CSR layer's local rows back on the host
+int n2v2r_get_layer_csr_nnz(n2v2r_handle* h, int k, int transpose, int64_t* nnz) {
+  if (h && h->multi()) return multi_get_layer_csr_nnz(h, k, transpose, nnz);
+  return guarded(h, [&]() -> int {
+    const LayerDev* L = nnz ? csr_layer_for_read(h, k, transpose) : nullptr;
+    if (!L) {
+      if (!nnz) h->err = "get_layer_csr_nnz: null output";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    *nnz = transpose ? L->t_nnz : L->nnz;
+    return N2V2R_OK;
+  });
+}
+
+int n2v2r_get_layer_csr(n2v2r_handle* h, int k, int transpose, int64_t* indptr, int32_t* indices,
+                        float* data) {
+  if (h && h->multi()) return multi_get_layer_csr(h, k, transpose, indptr, indices, data);
+  return guarded(h, [&]() -> int {
+    const LayerDev* L = indptr ? csr_layer_for_read(h, k, transpose) : nullptr;
+    if (!L) {
+      if (!indptr) h->err = "get_layer_csr: null output buffer";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    const CsrDev c = transpose ? L->csr_t() : L->csr();
+    if (c.nnz > 0 && (!indices || !data)) {
+      h->err = "get_layer_csr: null output buffer";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(indptr, c.indptr, sizeof(int64_t) * (c.n_rows + 1), hipMemcpyDeviceToHost));
+    if (c.nnz > 0) {
+      HIPCHK(hipMemcpy(indices, c.indices, sizeof(int32_t) * c.nnz, hipMemcpyDeviceToHost));
+      if (c.unit)  // (an unweighted layer may keep no value stream)
+        std::fill(data, data + c.nnz, 1.0f);
+      else
+        HIPCHK(hipMemcpy(data, c.data, sizeof(float) * c.nnz, hipMemcpyDeviceToHost));
+    }
+    return N2V2R_OK;
+  });
+}
+
+// diagnostics (n2v2r_diag.h): one kernel of the conversion alone, timed with HIP events
+int n2v2r_bench_sparsify_pass(n2v2r_handle* h, int k, int which, int reps, double* avg_ms,
+                              double* bytes) {
+  return guarded(h, [&]() -> int {
+    if (h->multi() || h->comm || k < 0 || k >= h->K || !h->layers[k]->loaded ||
+        !h->layers[k]->dense || which < 0 || which > 1 || reps < 1 || !avg_ms) {
+      h->err = "bench_sparsify_pass: a loaded dense layer of a one-GPU handle, which in [0, 1], "
+               "reps >= 1";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    const LayerDev& L = *h->layers[k];
+    hipStream_t st = h->stream;
+    const float* A = L.dA.as<float>();
+    DevBuf cnt;
+    CsrBuild b;
+    sparsify_count(h, A, L.lda, cnt, b);
+    b.ix.ensure_raw(sizeof(int32_t) * std::max<int64_t>(b.nnz, 1));
+    b.dv.ensure_raw(sizeof(float) * std::max<int64_t>(b.nnz, 1));
+    unsigned* flag = h->ing_flag.as<unsigned>();
+    auto launch = [&]() {
+      if (which == 0)
+        return n2v2r_launch_dense_row_count(A, h->nloc, L.lda, h->n, cnt.as<int64_t>(), flag, st);
+      return n2v2r_launch_dense_row_compact(A, h->nloc, L.lda, h->n, b.ip.as<int64_t>(),
+                                            b.ix.as<int32_t>(),
+                                            b.unit ? nullptr : b.dv.as<float>(), st);
+    };
+    HIPCHK(launch());  // warm-up
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    // one event pair around `reps` launches back to back, as tools/stream_ceiling.hip times its
+    // kernels
+    hipError_t err = hipEventRecord(e0, st);
+    for (int r = 0; r < reps && err == hipSuccess; ++r) err = launch();
+    if (err == hipSuccess) err = hipEventRecord(e1, st);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (err != hipSuccess) throw HipFail{err, "bench_sparsify_pass"};
+    *avg_ms = (double)ms / reps;
+    if (bytes) *bytes = 4.0 * (double)h->nloc * (double)L.lda;
+    return N2V2R_OK;
+  });
+}
+
 // diagnostics (n2v2r_diag.h): tom_tile_kernel alone, one HIP event pair per launch
 int n2v2r_bench_tom_tiles(n2v2r_handle* h, int k, int type, int reps, double* ms, double* flop) {
   return guarded(h, [&]() -> int {

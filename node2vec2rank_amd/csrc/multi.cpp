@@ -263,6 +263,76 @@ int multi_tom_layer(n2v2r_handle* h, int k, int type) {
   return fanout(h, [&](n2v2r_handle* r, int) { return n2v2r_tom_layer(r, k, type); });
 }
 
+// collective inside: each rank converts its own rows, the counts are summed and the failure
+// status is reduced before any rank commits; every rank returns the global counts
+int multi_layers_to_csr(n2v2r_handle* h, int64_t* nnz) {
+  std::vector<std::vector<int64_t>> rs(h->ranks.size(),
+                                       std::vector<int64_t>((size_t)std::max(h->K, 1)));
+  const int st = fanout(h, [&](n2v2r_handle* r, int i) {
+    return n2v2r_layers_to_csr(r, rs[i].data());
+  });
+  if (st == N2V2R_OK && nnz) std::copy(rs[0].begin(), rs[0].begin() + h->K, nnz);
+  return st;
+}
+
+int multi_count_layer_nonzeros(n2v2r_handle* h, int64_t* nnz) {
+  if (!nnz) {
+    h->err = "count_layer_nonzeros: null output buffer";
+    return N2V2R_ERR_BAD_ARG;
+  }
+  std::vector<std::vector<int64_t>> rs(h->ranks.size(),
+                                       std::vector<int64_t>((size_t)std::max(h->K, 1)));
+  const int st = fanout(h, [&](n2v2r_handle* r, int i) {
+    return n2v2r_count_layer_nonzeros(r, rs[i].data());
+  });
+  if (st == N2V2R_OK) std::copy(rs[0].begin(), rs[0].begin() + h->K, nnz);
+  return st;
+}
+
+// the entries of all N rows: the ranks' counts, one after the other
+int multi_get_layer_csr_nnz(n2v2r_handle* h, int k, int transpose, int64_t* nnz) {
+  if (!nnz) {
+    h->err = "get_layer_csr_nnz: null output";
+    return N2V2R_ERR_BAD_ARG;
+  }
+  std::vector<int64_t> rs(h->ranks.size(), 0);
+  const int st = fanout(h, [&](n2v2r_handle* r, int i) {
+    return n2v2r_get_layer_csr_nnz(r, k, transpose, &rs[i]);
+  });
+  if (st == N2V2R_OK) *nnz = std::accumulate(rs.begin(), rs.end(), (int64_t)0);
+  return st;
+}
+
+// rank r's rows land at row0 of the global row pointers, its entries behind the earlier ranks'
+int multi_get_layer_csr(n2v2r_handle* h, int k, int transpose, int64_t* indptr, int32_t* indices,
+                        float* data) {
+  if (!indptr) {
+    h->err = "get_layer_csr: null output buffer";
+    return N2V2R_ERR_BAD_ARG;
+  }
+  const size_t W = h->ranks.size();
+  std::vector<int64_t> rs(W, 0), off(W + 1, 0);
+  int st = fanout(h, [&](n2v2r_handle* r, int i) {
+    return n2v2r_get_layer_csr_nnz(r, k, transpose, &rs[i]);
+  });
+  if (st != N2V2R_OK) return st;
+  for (size_t i = 0; i < W; ++i) off[i + 1] = off[i] + rs[i];
+  if (off[W] > 0 && (!indices || !data)) {
+    h->err = "get_layer_csr: null output buffer";
+    return N2V2R_ERR_BAD_ARG;
+  }
+  st = fanout(h, [&](n2v2r_handle* r, int i) {
+    std::vector<int64_t> lip((size_t)r->nloc + 1);
+    const int s = n2v2r_get_layer_csr(r, k, transpose, lip.data(), indices + off[i],
+                                      data + off[i]);
+    if (s != N2V2R_OK) return s;
+    for (int64_t j = 0; j < r->nloc; ++j) indptr[r->row0 + j] = lip[j] + off[i];
+    return (int)N2V2R_OK;
+  });
+  if (st == N2V2R_OK) indptr[h->n] = off[W];
+  return st;
+}
+
 // rank r's rows land at row0 of the caller's n x n array (disjoint bands)
 int multi_get_layer_dense(n2v2r_handle* h, int k, float* A) {
   if (!A) {

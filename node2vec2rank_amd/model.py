@@ -12,7 +12,13 @@ Differences a user can observe (documented in DESIGN.md):
     exact ties as the reference does (pandas ``sort_values`` = numpy quicksort, model.py:173-174,
     an implementation-defined order of equal values); the GPU flags such columns and sums their
     positions.  ``tie_order="stable"`` (constructor) keeps the GPU's stable order instead:
-    equal values by ascending node index.  Tie-free columns are sorted on the GPU either way.
+    equal values by ascending node index.  Tie-free columns are sorted on the GPU either way;
+  * ``sparsify=True`` / ``"auto"`` (constructor; default ``False``): layers the engine holds in
+    dense storage (``Coexpression`` layers after their threshold / top-percent / binarize, dense
+    arrays) are converted to CSR in HBM before the fit, always or when every layer is at most 1/4
+    non-zero.  The matrices are the same; the fit then runs the sparse products, whose fp32 sums
+    add in another order than the dense GEMMs' (embeddings and DeDi agree within fp32 rounding,
+    not bit for bit).
 """
 from __future__ import annotations
 
@@ -64,7 +70,7 @@ class N2V2R:
 
     def __init__(self, graphs: list, nodes: list, config: dict, device: int = 0,
                  eig_options: dict | None = None, tie_order: str = "reference",
-                 n_gpus: int | None = None, devices: list | None = None):
+                 n_gpus: int | None = None, devices: list | None = None, sparsify=False):
         self.config = config
         self.node_names = nodes
         self.graphs = graphs
@@ -112,6 +118,9 @@ class N2V2R:
             raise ValueError(f"unknown tie_order {tie_order!r}")
         self.tie_order = tie_order
         self._eig_options = dict(eig_options or {})
+        # Engine.set_layers(sparsify=...): dense-storage layers (Coexpression layers, dense
+        # arrays) converted to CSR in HBM after the last one is built and transformed
+        self._sparsify = sparsify
         self._layers_loaded = False
         self._keys = None
         self._cols = None
@@ -155,7 +164,7 @@ class N2V2R:
     def _load_layers(self):
         eng = self._engine
         if not self._layers_loaded:
-            eng.set_layers([_as_layer(g) for g in self.graphs])
+            eng.set_layers([_as_layer(g) for g in self.graphs], sparsify=self._sparsify)
             self._layers_loaded = True
         return eng
 
