@@ -333,6 +333,8 @@ int n2v2r_pairwise_distances(n2v2r_handle* h, const double* m1, const double* m2
                              int dim, int metric, double* out);
 int n2v2r_borda_columns(n2v2r_handle* h, const double* D /* C*N column-major */, int64_t n,
                         int n_cols, int64_t* borda);
+/* Row sums of the stored A^T (of A when symmetric); an unweighted layer's entries count 1.0f each:
+ * its A^T copy keeps no value stream, and none is read. */
 int n2v2r_column_sums(n2v2r_handle* h, int k, float* out /* N */);
 /* n2v2r_borda_columns with the reference's tie order within the caller's reach
  * (aggregate_transform, model.py:167-185).  The GPU sort is stable: equal values rank by

@@ -12,9 +12,9 @@
 // an unsorted A is compared through (A^T)^T.
 #include "common.h"
 
-// One wave per row: flags bit 0 = a column index outside [0, n), bit 1 = a value != 1.0f,
-// bit 2 = a row whose column indices are not ascending.  keys / idx (optional) receive the
-// transpose sort's input.
+// One wave per row: flags bit 0 = a column index outside [0, n), bit 1 = a value != 1.0f
+// (dv == nullptr: a unit CSR without a value stream, never set), bit 2 = a row whose column
+// indices are not ascending.  keys / idx (optional) receive the transpose sort's input.
 __global__ __launch_bounds__(256) void csr_scan_kernel(const int64_t* __restrict__ ip,
                                                        const int32_t* __restrict__ ix,
                                                        const float* __restrict__ dv, int64_t n_rows,
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void csr_scan_kernel(const int64_t* __restrict
       const int32_t c = ix[p];
       const bool bad = c < 0 || (int64_t)c >= n_cols;
       f |= bad ? 1u : 0u;
-      f |= (dv[p] != 1.0f) ? 2u : 0u;
+      f |= (dv && dv[p] != 1.0f) ? 2u : 0u;
       if (p > p0 && ix[p - 1] > c) f |= 4u;
       if (keys) {
         keys[p] = ((uint64_t)(uint32_t)(bad ? 0 : c) << 32) | (uint64_t)(uint32_t)r;

@@ -113,8 +113,9 @@ void ensure_colcsr(LayerDev& L, int64_t ncols, int64_t rows_out, hipStream_t st,
     }
     flag.ensure(sizeof(unsigned) * 4, st);
     HIPCHK(hipMemsetAsync(flag.p, 0, sizeof(unsigned) * 4, st));
-    HIPCHK(n2v2r_launch_csr_scan(s.indptr, s.indices, s.data, s.n_rows, ncols,
-                                 keys[0].as<uint64_t>(), pay[0].as<int32_t>(),
+    // (a unit A^T copy keeps no value stream; the scan's flags are not read here)
+    HIPCHK(n2v2r_launch_csr_scan(s.indptr, s.indices, s.unit ? nullptr : s.data, s.n_rows,
+                                 ncols, keys[0].as<uint64_t>(), pay[0].as<int32_t>(),
                                  flag.as<unsigned>(), st));
     if (rc > 0)
       HIPCHK(n2v2r_launch_chunk_major_keys(keys[0].as<uint64_t>(), nnz, npad, W, rc, st));

@@ -906,13 +906,15 @@ extern "C" hipError_t n2v2r_launch_cb_fill(const CsrDev& A, int64_t cw, int nb, 
 
 // Column sums of a CSR layer (DeDi, model.py:282-311): out[j] = sum_i A[i][j].  fp32
 // atomics would make the order run-dependent, so the engine calls this on A^T (row sums of
-// the transpose = column sums) when the layer is not symmetric.
+// the transpose = column sums) when the layer is not symmetric.  An unweighted layer counts
+// its entries: the A^T copy of one keeps no value stream (layers.cpp n2v2r_set_layer_csr).
 __global__ void csr_row_sums_kernel(CsrDev A, float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (row >= A.n_rows) return;
   float s = 0.f;
-  for (int64_t p = A.indptr[row] + lane; p < A.indptr[row + 1]; p += 64) s += A.data[p];
+  for (int64_t p = A.indptr[row] + lane; p < A.indptr[row + 1]; p += 64)
+    s += A.unit ? 1.f : A.data[p];
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
   if (lane == 0) out[row] = s;

@@ -1,7 +1,10 @@
 """CSR ingest on the GPU (n2v2r_set_layer_csr): range check, unweighted detection, the stable
 radix transpose and the symmetry test, on the inputs a caller may hand over uncanonical
-(unsorted rows, duplicate entries, empty rows, an empty layer).  A^T X through the stored
-transpose is checked against scipy; a wrong symmetric verdict would fail it."""
+(unsorted rows, duplicate entries, empty rows, an empty layer).  This file only multiplies: A X
+and A^T X through whatever the ingest stored are checked against scipy to an fp32 tolerance,
+which a wrong symmetric verdict on a clearly directed layer fails.  The stored rows of A, the
+A^T copy and the verdict itself are compared entry by entry, bitwise, in
+test_gpu_ingest_structure.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -51,7 +54,7 @@ def test_unsorted_rows(engine, symmetric, weighted):
     engine.set_layers([U])
     _check_products(engine, A, rng)
     # the symmetry verdict: a symmetric layer keeps no transpose, a directed one does; both
-    # give the same products, so compare the stored transpose with scipy explicitly
+    # give the same products, so multiply through a transpose that is kept in any case
     engine.set_layers([U], symmetric=0)
     _check_products(engine, A, rng)
 
