@@ -83,6 +83,34 @@ typedef struct n2v2r_gram_info {
 int n2v2r_gram_apply(n2v2r_handle* h, int b, const float* X, float* Z, float* W,
                      n2v2r_gram_info* info);
 
+/* What one n2v2r_ritz_step launched, as the solver's ritz_vectors recorded it. */
+typedef struct n2v2r_ritz_info {
+  int fused;     /* 1: ritz_nn_kernel made X (and MX) in one launch; 0: ts_nn launches per slice */
+  int launches;  /* product launches made: 1 when fused, else one per slice of <= 128 output
+                    columns and product (X, and MX unless lean) */
+  int lds_bytes; /* dynamic LDS of the fused launch (the launcher's rule), else 0 */
+} n2v2r_ritz_info;
+
+/* The step between a cycle's Rayleigh-Ritz and the next cycle alone (tests), through the solver's
+ * own ritz_vectors and launch_residuals on an Eig whose plan is block width b (8, 16, 32 or 64),
+ * keep kept Ritz vectors and a basis of nq blocks, with the fit's scratch sizing: X = Q S and
+ * MX = W S (fused at b = 8, keep <= 96 while S fits 150 KB of LDS, else per slice of 128 output
+ * columns), then res[j] = sum_r (MX[r][j] - theta[j] X[r][j])^2.  n = the handle's local row
+ * count, from the layers set (any loaded layers; the step does not read them).
+ * Q, W: nq blocks of n x b fp32, one after the other; S: (nq b) x keep fp32 row-major; theta: keep
+ * fp64.  X, MX: keep / b blocks of n x b fp32; res: keep fp64.  lean != 0 (b = 8 only): X alone,
+ * as a fit with lean images computes it; W, MX and res may be NULL and are not touched.  Every row
+ * of X and MX the step has to write, and res, is filled with NaN bytes first.  On a rank handle
+ * every rank makes the call with its own rows (collective unless lean) and res comes back summed
+ * over the ranks, as the solver reads it.  info (optional): what ran.  The handle's embedding
+ * and ranking results are left alone, and a later fit is bit-identical to one without the call.
+ * N2V2R_ERR_BAD_ARG on a multi-GPU parent handle, without loaded layers, for another b, for
+ * keep % b != 0, keep + b > nq b, nq b > 768, lean with b != 8, and for a NULL pointer the mode
+ * needs. */
+int n2v2r_ritz_step(n2v2r_handle* h, int b, int nq, int keep, int lean, const float* Q,
+                    const float* W, const float* S, const double* theta, float* X, float* MX,
+                    double* res, n2v2r_ritz_info* info);
+
 /* Banded Rayleigh-Ritz stage alone (tests; block width 8, c <= 512, kp + 8 <= 192): the
  * projected matrix of a Krylov-Schur cycle given as UASE keeps it.  Basis order [X (kp
  * columns, diagonal theta_prev), E, Z_2, ...] in 8-wide blocks; hband holds band column

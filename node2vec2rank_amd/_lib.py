@@ -53,7 +53,7 @@ EXPORTED = [
     "n2v2r_create_multi", "n2v2r_multi_devices", "n2v2r_h2d_layer_bytes",
     "n2v2r_set_layer_corr", "n2v2r_get_layer_dense", "n2v2r_transform_layer",
     "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles", "n2v2r_pip_pass",
-    "n2v2r_gram_apply", "n2v2r_layers_to_csr", "n2v2r_count_layer_nonzeros",
+    "n2v2r_gram_apply", "n2v2r_ritz_step", "n2v2r_layers_to_csr", "n2v2r_count_layer_nonzeros",
     "n2v2r_get_layer_csr_nnz", "n2v2r_get_layer_csr", "n2v2r_bench_sparsify_pass",
 ]
 UNIQUE_ID_BYTES = 128
@@ -95,6 +95,10 @@ class EigStats(ctypes.Structure):
 class GramInfo(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int) for k in ("form", "rs_form", "rs_chunks", "split2", "tile_nb",
                                             "tile_wb", "tile_rows", "rpw1", "rpw2")]
+
+
+class RitzInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("fused", "launches", "lds_bytes")]
 
 
 class TransformStats(ctypes.Structure):
@@ -171,6 +175,8 @@ def load(path: str | None = None):
                                     _p(np.int32), _p(np.int32), _p(np.int32)]),
             "n2v2r_gram_apply": (_i, [_vp, _i, _p(np.float32), _vp, _p(np.float32),
                                       ctypes.POINTER(GramInfo)]),
+            "n2v2r_ritz_step": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     ctypes.POINTER(RitzInfo)]),
             "n2v2r_rr_band_top": (_i, [_vp, _i, _i, _p(np.float64), ctypes.c_int64, _vp, _i,
                                        _p(np.float64), _p(np.float32)]),
             "n2v2r_set_layer_dense": (_i, [_vp, _i, _i64, _p(np.float32), _i]),
@@ -840,6 +846,36 @@ class Engine:
             self.h, int(b), X, Z.ctypes.data_as(ctypes.c_void_p) if want_z else None, W,
             ctypes.byref(info)), "gram_apply")
         return W, Z, {k: getattr(info, k) for k, _ in GramInfo._fields_}
+
+    def ritz_step(self, Q, W, S, theta, lean: bool = False):
+        """The step between Rayleigh-Ritz and the next cycle alone (see n2v2r_ritz_step).  Q, W:
+        (nq, n_local, b) fp32 basis blocks and images (W None when lean); S: (nq b, keep) fp32;
+        theta: keep fp64.  Returns (X, MX, res, info): (keep / b, n_local, b) fp32 blocks (MX and
+        res None when lean), keep fp64 squared residuals and a dict of n2v2r_ritz_info's fields."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        W = None if W is None else np.ascontiguousarray(W, dtype=np.float32)
+        nl = self._n_local()
+        if Q.ndim != 3 or Q.shape[1] != nl or (W is not None and W.shape != Q.shape):
+            raise ValueError(f"ritz_step: Q and W must be (nq, {nl}, b), got {Q.shape}")
+        nq, b = Q.shape[0], Q.shape[2]
+        if S.ndim != 2 or S.shape[0] != nq * b or theta.shape != (S.shape[1],):
+            raise ValueError("ritz_step: S must be (nq b, keep) and theta (keep,)")
+        keep = S.shape[1]
+        pb = max(1, keep // max(b, 1))
+        X = np.empty((pb, nl, b), dtype=np.float32)
+        MX = None if lean else np.empty((pb, nl, b), dtype=np.float32)
+        res = None if lean else np.empty(keep, dtype=np.float64)
+        info = RitzInfo()
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+        self._check(self.lib.n2v2r_ritz_step(
+            self.h, int(b), int(nq), int(keep), int(bool(lean)), ptr(Q), ptr(W), ptr(S),
+            ptr(theta), ptr(X), ptr(MX), ptr(res), ctypes.byref(info)), "ritz_step")
+        return X, MX, res, {k: getattr(info, k) for k, _ in RitzInfo._fields_}
 
     def rr_band_top(self, hband, c: int, kp: int, theta_prev, p: int):
         """Banded Rayleigh-Ritz stage alone (see n2v2r_rr_band_top).  Returns (w, S)."""

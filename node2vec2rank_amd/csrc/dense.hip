@@ -1299,6 +1299,12 @@ __global__ __launch_bounds__(RZ_T) void ritz_nn_kernel(BlockList A0, BlockList A
   }
 }
 
+// dynamic LDS of a ritz_nn launch: the coefficients of a_blocks 8-wide blocks, cb columns padded
+// to whole 32-wide tiles
+extern "C" size_t n2v2r_ritz_nn_lds_bytes(int a_blocks, int cb) {
+  return sizeof(float) * (size_t)a_blocks * 8 * ((cb + 31) / 32) * 32;
+}
+
 // X = Q S and MX = W S (O1.count == 0: X only); hipErrorNotSupported when the coefficients do
 // not fit one CU's LDS (the caller then uses n2v2r_launch_ts_nn per product)
 extern "C" hipError_t n2v2r_launch_ritz_nn(const BlockList& A0, const BlockList& A1, const float* G,
@@ -1310,7 +1316,7 @@ extern "C" hipError_t n2v2r_launch_ritz_nn(const BlockList& A0, const BlockList&
   if (O1.count > 0 && (A1.count != A0.count || A1.width != 8 || O1.width != O0.width))
     return hipErrorInvalidValue;
   const int nt = (cb + 31) / 32;
-  const size_t lds = sizeof(float) * (size_t)A0.count * 8 * nt * 32;
+  const size_t lds = n2v2r_ritz_nn_lds_bytes(A0.count, cb);
   if (lds > 150 * 1024) return hipErrorNotSupported;
   static bool attr = false;
   if (!attr) {

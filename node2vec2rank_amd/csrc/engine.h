@@ -58,6 +58,7 @@ hipError_t n2v2r_launch_cb_fill(const CsrDev& A, int64_t cw, int nb, const int64
 hipError_t n2v2r_launch_ritz_nn(const BlockList& A0, const BlockList& A1, const float* G, int ldg,
                                 int cb, const OutBlockList& O0, const OutBlockList& O1, int64_t n,
                                 int grid, hipStream_t stream);
+size_t n2v2r_ritz_nn_lds_bytes(int a_blocks, int cb);
 hipError_t n2v2r_launch_ts_nn(const BlockList& A, const float* G, int ldg, int cb,
                               const OutBlockList& O, const BlockList& C, float alpha, float beta,
                               int64_t n, hipStream_t stream);

@@ -241,6 +241,10 @@ struct Eig {
   float* pending = nullptr;  // the W block whose value still sits in the partials
   // rows per wave of the last row-kernel launch of stage 1 / stage 2 (0: none yet; diagnostics)
   int rpw1 = 0, rpw2 = 0;
+  // the last ritz_vectors: whether the fused kernel made the products, and the product launches
+  // (1 fused; else one ts_nn launch per slice and product) (diagnostics)
+  bool ritz_done = false;
+  int ritz_launches = 0;
   int stats_rr_fallbacks = 0;  // Sturm Rayleigh-Ritz cycles redone by the reducing path
   // dense Rayleigh-Ritz: the multi-workgroup tridiagonalisation's error word of the current
   // cycle (nullptr: the one-workgroup kernel ran), and whether a timeout switched the fit to the
@@ -1226,7 +1230,8 @@ struct Eig {
   void ritz_vectors(int nq) {
     lds_poison();
     const int per_launch = std::max(1, 128 / b);  // output blocks per ts_nn launch (<= 128 cols)
-    bool ritz_done = false;
+    ritz_done = false;
+    ritz_launches = 0;
     if (b == 8 && keep <= 96) {
       // both products in one launch (ritz_nn_kernel), the coefficients staged once per CU
       OutBlockList ox{}, omx{};
@@ -1242,6 +1247,7 @@ struct Eig {
                                                 n, 0, st);
       if (e == hipSuccess) ritz_done = true;
       else if (e != hipErrorNotSupported) throw HipFail{e, "n2v2r_launch_ritz_nn"};
+      ritz_launches = ritz_done ? 1 : 0;
     }
     for (int q0b = 0; !ritz_done && q0b < pb; q0b += per_launch) {
       const int nt = std::min(per_launch, pb - q0b);
@@ -1259,6 +1265,7 @@ struct Eig {
       if (!lean)
         HIPCHK(n2v2r_launch_ts_nn(blocks(W, 0, nq), g, keep, nt * b, omx, one(nullptr), 1.f, 0.f,
                                   n, st));
+      ritz_launches += lean ? 1 : 2;
     }
     for (int q = 0; q < pb; ++q) {
       dbg(X[q], n * b, false, "Ritz vectors X = Q S");
@@ -1988,6 +1995,83 @@ int n2v2r_gram_apply(n2v2r_handle* h, int b, const float* X, float* Z, float* W,
       info->tile_rows = eig.col_blocks ? eig.tile_rows : 0;
       info->rpw1 = eig.rpw1;
       info->rpw2 = eig.rpw2;
+    }
+    return N2V2R_OK;
+  });
+}
+
+// One restart step alone (tests): an Eig set up as a fit's with the given plan, its ritz_vectors
+// and launch_residuals on host arrays.
+int n2v2r_ritz_step(n2v2r_handle* h, int b, int nq, int keep, int lean, const float* Q,
+                    const float* W, const float* S, const double* theta, float* X, float* MX,
+                    double* res, n2v2r_ritz_info* info) {
+  return guarded(h, [&]() -> int {
+    if (h->multi() || (b != 8 && b != 16 && b != 32 && b != 64) || nq < 1 || keep < b ||
+        keep % b != 0 || (int64_t)keep + b > (int64_t)nq * b || (int64_t)nq * b > N2V2R_BAND_MAXC ||
+        (lean && b != 8) || !Q || !S || !theta || !X || (!lean && (!W || !MX || !res)))
+      return N2V2R_ERR_BAD_ARG;
+    if (h->K < 1) {
+      h->err = "no layers set";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    for (auto& L : h->layers)
+      if (!L->loaded) {
+        h->err = "a layer was not loaded";
+        return N2V2R_ERR_BAD_ARG;
+      }
+    Eig eig{};
+    eig.h = h;
+    eig.st = h->stream;
+    eig.n = h->nloc;
+    eig.npad = h->npad;
+    eig.row0 = h->row0;
+    eig.K = h->K;
+    eig.b = b;
+    eig.keep = keep;
+    eig.pb = keep / b;
+    eig.nb_max = nq;
+    eig.c_max = nq * b;
+    eig.stats = nullptr;
+    eig.reuse_pool();
+    eig.size_scratch();
+    eig.lean = lean != 0;  // (size_scratch chose what a fit of this plan would take)
+    hipStream_t st = eig.st;
+    const int pb = eig.pb;
+    const size_t rows = sizeof(float) * (size_t)eig.n * b;
+    for (int q = 0; q < nq; ++q) {
+      eig.Q.push_back(eig.take());
+      HIPCHK(hipMemcpyAsync(eig.Q[q], Q + (size_t)q * eig.n * b, rows, hipMemcpyHostToDevice, st));
+      if (eig.lean) continue;
+      eig.W.push_back(eig.take());
+      HIPCHK(hipMemcpyAsync(eig.W[q], W + (size_t)q * eig.n * b, rows, hipMemcpyHostToDevice, st));
+    }
+    // NaN bytes in every row the step has to write
+    for (int q = 0; q < pb; ++q) {
+      eig.X.push_back(eig.take());
+      eig.MX.push_back(eig.lean ? nullptr : eig.take());
+      HIPCHK(hipMemsetAsync(eig.X[q], 0xFF, rows, st));
+      if (!eig.lean) HIPCHK(hipMemsetAsync(eig.MX[q], 0xFF, rows, st));
+    }
+    HIPCHK(hipMemsetAsync(h->resid.p, 0xFF, sizeof(double) * keep, st));
+    HIPCHK(hipMemcpyAsync(h->ews.csmall.p, S, sizeof(float) * (size_t)nq * b * keep,
+                          hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->theta.p, theta, sizeof(double) * keep, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // pageable sources: complete before the kernels
+    eig.ritz_vectors(nq);
+    if (!eig.lean) eig.launch_residuals();
+    for (int q = 0; q < pb; ++q) {
+      HIPCHK(hipMemcpyAsync(X + (size_t)q * eig.n * b, eig.X[q], rows, hipMemcpyDeviceToHost, st));
+      if (!eig.lean)
+        HIPCHK(hipMemcpyAsync(MX + (size_t)q * eig.n * b, eig.MX[q], rows, hipMemcpyDeviceToHost,
+                              st));
+    }
+    if (!eig.lean)
+      HIPCHK(hipMemcpyAsync(res, h->resid.p, sizeof(double) * keep, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (info) {
+      info->fused = eig.ritz_done ? 1 : 0;
+      info->launches = eig.ritz_launches;
+      info->lds_bytes = eig.ritz_done ? (int)n2v2r_ritz_nn_lds_bytes(nq, keep) : 0;
     }
     return N2V2R_OK;
   });
