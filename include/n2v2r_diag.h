@@ -111,6 +111,61 @@ int n2v2r_ritz_step(n2v2r_handle* h, int b, int nq, int keep, int lean, const fl
                     const float* W, const float* S, const double* theta, float* X, float* MX,
                     double* res, n2v2r_ritz_info* info);
 
+/* What one n2v2r_block_gram or n2v2r_ortho_pass launched, from the launchers' own shape rules
+ * (the functions the launchers call to decide). */
+typedef struct n2v2r_pass_info {
+  int gram_form;    /* the Gram kernel: 0 streaming (b = 8), 1 lines (b = 8), 2 narrow (one 8- or
+                       16-wide right-hand block), 3 MFMA tiles */
+  int gram_flush;   /* narrow form: 1 when the instantiation that flushes its fp32 sums ran */
+  int64_t nchunks;  /* row chunks of the Gram (one fp64 partial each) */
+  int64_t rows_per_chunk; /* rows of a chunk; its 4 waves take ceil(rows_per_chunk / 4) each */
+  int stage;        /* pass, b > 8: 1 when pip_chol staged the Gram through LDS (b = 8: 0) */
+  int nwg;          /* pass, b > 8: the workgroups F's rows were split over (b = 8: 0) */
+  int apply_kernel; /* pass: 0 the fused b = 8 kernel, 8 / 16 ts_nn_rows_kernel<8> / <16>,
+                       32 NT ts_nn_kernel<NT> */
+  int reserved;
+  uint64_t fill_seed; /* pass: the refill seed the pass drew (Eig::next_fill_seed) */
+} n2v2r_pass_info;
+
+/* G = [A]^T [B] alone (tests), through the solver's own Gram method (Eig::tn) on an Eig whose plan
+ * is block width b (8, 16, 32 or 64) and a basis of max(na, nb) blocks, with the fit's scratch
+ * sizing, so the partial buffer and with it the chunk plan are a fit's: the pass Gram
+ * [Q Z]^T Z (nb = 1) and the projected matrix H = Q^T W of the dense Rayleigh-Ritz (na = nb).
+ * n = the handle's local row count, from the layers set (any loaded layers; the call does not
+ * read them).  A, B: na / nb blocks of n x b fp32, one after the other; G: (na b) x (nb b) fp64
+ * row-major, filled with NaN bytes first, like the chunk partials.  info (optional): what ran.
+ * The handle's embedding and ranking results are left alone, and a later fit is bit-identical to
+ * one without the call.  One-GPU handles only: N2V2R_ERR_BAD_ARG on a rank or multi-GPU handle,
+ * without loaded layers, for another b, for na < 1, nb < 1, na b > 768 or nb b > 768, and for a
+ * NULL A, B or G. */
+int n2v2r_block_gram(n2v2r_handle* h, int b, int na, int nb, const float* A, const float* B,
+                     double* G, n2v2r_pass_info* info);
+
+/* One orthogonalisation pass at block width b (8, 16, 32 or 64) alone (tests), through the
+ * solver's own Eig::pip_pass on an Eig whose plan is b and a basis of nq + 1 blocks, with the
+ * fit's scratch sizing: the Gram [Q Z]^T Z, then at b = 8 the fused pass, at wider blocks
+ * pip_chol (P = Z^T Z - C^T C, its Cholesky factor's inverse, F = [-C R^{-1}; R^{-1}]) and the
+ * apply Z' = [Q Z] F.  n = the handle's local row count, as for n2v2r_block_gram.
+ * Q: nq >= 0 basis blocks of n x b fp32 (nq = 0: the start block's pass, Q may be NULL); Z: n x b
+ * fp32, the block in and the result out.  in_place = 0: the pass reads a separate copy of Z and
+ * writes a block filled with NaN bytes, as an expansion does from the image it orthogonalises.
+ * first: as PipPass::first (a pivot the Gram cannot resolve is clamped and the column kept).
+ * cond: -1 no condition word; 0 / 1: that value in a device word the pass is conditional on (the
+ * third pass's gate; 0: nothing runs, the flags and any_flag are cleared).  seed: the Eig's seed,
+ * from which the pass draws its refill seed (returned in info).
+ * gram: (nq + 1) b x b fp64; xinv: b x b fp64 (R^{-1}, flagged columns zero; b = 8: not written,
+ * the fused kernel keeps it in LDS); F: (nq + 1) b x b fp32 (b = 8: not written); flags[b],
+ * any_flag.  The device buffers behind gram, xinv, F and the result block are filled with NaN
+ * bytes before the pass and the flag words with a non-zero pattern, so what no launch wrote shows.
+ * The handle's embedding and ranking results are left alone, and a later fit is bit-identical to
+ * one without the call.  One-GPU handles only: N2V2R_ERR_BAD_ARG on a rank or multi-GPU handle,
+ * without loaded layers, for another b, for nq < 0, (nq + 1) b > 768, cond outside -1 .. 1, and
+ * for a NULL pointer the mode needs (Q with nq > 0, Z, gram, flags, any_flag; xinv and F at
+ * b > 8). */
+int n2v2r_ortho_pass(n2v2r_handle* h, int b, int nq, const float* Q, float* Z, int in_place,
+                     int first, int cond, uint64_t seed, double* gram, double* xinv, float* F,
+                     int* flags, int* any_flag, n2v2r_pass_info* info);
+
 /* Banded Rayleigh-Ritz stage alone (tests; block width 8, c <= 512, kp + 8 <= 192): the
  * projected matrix of a Krylov-Schur cycle given as UASE keeps it.  Basis order [X (kp
  * columns, diagonal theta_prev), E, Z_2, ...] in 8-wide blocks; hband holds band column

@@ -55,6 +55,7 @@ EXPORTED = [
     "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles", "n2v2r_pip_pass",
     "n2v2r_gram_apply", "n2v2r_ritz_step", "n2v2r_layers_to_csr", "n2v2r_count_layer_nonzeros",
     "n2v2r_get_layer_csr_nnz", "n2v2r_get_layer_csr", "n2v2r_bench_sparsify_pass",
+    "n2v2r_block_gram", "n2v2r_ortho_pass",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -99,6 +100,17 @@ class GramInfo(ctypes.Structure):
 
 class RitzInfo(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int) for k in ("fused", "launches", "lds_bytes")]
+
+
+class PassInfo(ctypes.Structure):
+    _fields_ = [("gram_form", ctypes.c_int), ("gram_flush", ctypes.c_int),
+                ("nchunks", ctypes.c_int64), ("rows_per_chunk", ctypes.c_int64),
+                ("stage", ctypes.c_int), ("nwg", ctypes.c_int), ("apply_kernel", ctypes.c_int),
+                ("reserved", ctypes.c_int), ("fill_seed", ctypes.c_uint64)]
+
+
+# n2v2r_pass_info.gram_form
+GRAM_STREAM, GRAM_LINES, GRAM_NARROW, GRAM_MFMA = 0, 1, 2, 3
 
 
 class TransformStats(ctypes.Structure):
@@ -177,6 +189,9 @@ def load(path: str | None = None):
                                       ctypes.POINTER(GramInfo)]),
             "n2v2r_ritz_step": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(RitzInfo)]),
+            "n2v2r_block_gram": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, ctypes.POINTER(PassInfo)]),
+            "n2v2r_ortho_pass": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, ctypes.c_uint64, _vp,
+                                      _vp, _vp, _vp, _vp, ctypes.POINTER(PassInfo)]),
             "n2v2r_rr_band_top": (_i, [_vp, _i, _i, _p(np.float64), ctypes.c_int64, _vp, _i,
                                        _p(np.float64), _p(np.float32)]),
             "n2v2r_set_layer_dense": (_i, [_vp, _i, _i64, _p(np.float32), _i]),
@@ -876,6 +891,52 @@ class Engine:
             self.h, int(b), int(nq), int(keep), int(bool(lean)), ptr(Q), ptr(W), ptr(S),
             ptr(theta), ptr(X), ptr(MX), ptr(res), ctypes.byref(info)), "ritz_step")
         return X, MX, res, {k: getattr(info, k) for k, _ in RitzInfo._fields_}
+
+    def block_gram(self, A, B):
+        """G = [A]^T [B] through the solver's own Gram method (see n2v2r_block_gram).  A, B:
+        (na, n_local, b) and (nb, n_local, b) fp32 blocks.  Returns (G, info): (na b, nb b) fp64
+        and a dict of n2v2r_pass_info's fields."""
+        A = np.ascontiguousarray(A, dtype=np.float32)
+        B = np.ascontiguousarray(B, dtype=np.float32)
+        nl = self._n_local()
+        if A.ndim != 3 or B.ndim != 3 or A.shape[1:] != B.shape[1:] or A.shape[1] != nl:
+            raise ValueError(f"block_gram: A and B must be (blocks, {nl}, b), got {A.shape}, "
+                             f"{B.shape}")
+        na, nb, b = A.shape[0], B.shape[0], A.shape[2]
+        G = np.empty((na * b, nb * b), dtype=np.float64)
+        info = PassInfo()
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self.lib.n2v2r_block_gram(self.h, int(b), int(na), int(nb), vp(A), vp(B),
+                                              vp(G), ctypes.byref(info)), "block_gram")
+        return G, {k: getattr(info, k) for k, _ in PassInfo._fields_}
+
+    def ortho_pass(self, Q, Z, in_place: bool = True, first: int = 0, cond: int = -1,
+                   seed: int = 1):
+        """One orthogonalisation pass at block width b alone (see n2v2r_ortho_pass).  Q:
+        (nq, n_local, b) fp32, nq >= 0; Z: (n_local, b) fp32.  Returns a dict: Z after the pass,
+        the fp64 Gram ((nq + 1) b, b), xinv (b, b) and F ((nq + 1) b, b) (both None at b = 8),
+        flags, any_flag and info (n2v2r_pass_info's fields)."""
+        z = np.array(Z, dtype=np.float32, order="C")
+        nl = self._n_local()
+        if z.ndim != 2 or z.shape[0] != nl:
+            raise ValueError(f"ortho_pass: Z must be ({nl}, b), got {z.shape}")
+        b = z.shape[1]
+        Q = np.ascontiguousarray(Q, dtype=np.float32).reshape(-1, nl, b)
+        nq = Q.shape[0]
+        gram = np.empty(((nq + 1) * b, b), dtype=np.float64)
+        xinv = None if b == 8 else np.empty((b, b), dtype=np.float64)
+        F = None if b == 8 else np.empty(((nq + 1) * b, b), dtype=np.float32)
+        flags = np.empty(b, dtype=np.int32)
+        any_flag = np.empty(1, dtype=np.int32)
+        info = PassInfo()
+        vp = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self.lib.n2v2r_ortho_pass(
+            self.h, int(b), int(nq), vp(Q), vp(z), int(bool(in_place)), int(first), int(cond),
+            int(seed), vp(gram), vp(xinv), vp(F), vp(flags), vp(any_flag), ctypes.byref(info)),
+            "ortho_pass")
+        return {"Z": z, "gram": gram, "xinv": xinv, "F": F, "flags": flags,
+                "any_flag": int(any_flag[0]),
+                "info": {k: getattr(info, k) for k, _ in PassInfo._fields_}}
 
     def rr_band_top(self, hband, c: int, kp: int, theta_prev, p: int):
         """Banded Rayleigh-Ritz stage alone (see n2v2r_rr_band_top).  Returns (w, S)."""

@@ -658,39 +658,31 @@ static int64_t stream_chunks(int64_t n, int waves, int blocks, int64_t* rows) {
   return (n + *rows - 1) / *rows;
 }
 
-static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n,
-                               double* partial, size_t partial_elems, double* out,
-                               const int* cond, const ZSum* zs, hipStream_t stream) {
-  const int ca = A.count * A.width, cb = B.count * B.width;
-  int64_t s_chunks = 0, s_rows = 0;
-  if (B.count == 1 && B.width == 8 && A.width == 8) {
+// Which Gram form launch_ts_tn takes for a shape, and its chunk plan: the launcher's own decision
+// (it launches what this returns; the diagnostic entries report it).  hipErrorInvalidValue when
+// the partial buffer cannot hold one chunk's partial.
+extern "C" hipError_t n2v2r_ts_tn_plan(int a_count, int a_width, int b_count, int b_width,
+                                       int64_t n, size_t partial_elems, TnPlan* plan) {
+  const int ca = a_count * a_width, cb = b_count * b_width;
+  const int64_t elems = (int64_t)ca * cb;
+  plan->flush = 0;
+  if (b_count == 1 && b_width == 8 && a_width == 8) {
     // streaming form: ~TN_STREAM_WAVES (4096) waves, chunks of <= TS_MAX_CHUNK rows, nchunks % 8 == 0
     // (<= 4 blocks -- the local pass -- aim at half the waves: longer chunks, half the partials
     // to reduce; cfg4 Gram 30.1 -> 28.4 us and reduce 7.0 -> 5.0 us per pass, 1024 / 8192 worse;
     // profiles/r04_tn_small_waves.txt)
-    s_chunks = stream_chunks(n, A.count <= 4 ? TN_STREAM_WAVES / 2 : TN_STREAM_WAVES, A.count, &s_rows);
+    int64_t s_rows = 0;
+    const int64_t s_chunks =
+        stream_chunks(n, a_count <= 4 ? TN_STREAM_WAVES / 2 : TN_STREAM_WAVES, a_count, &s_rows);
     // partials must fit the buffer; otherwise the line form below takes it
-    if ((size_t)(s_chunks * ca * cb) > partial_elems || s_rows > TS_MAX_CHUNK) s_chunks = 0;
-  }
-  if (s_chunks > 0) {
-    const int64_t elems = (int64_t)ca * cb;
-    const int64_t nchunks = s_chunks, rows_per_chunk = s_rows;
-    const dim3 grid((unsigned)nchunks, (unsigned)((A.count + 3) / 4));
-    if (zs && zs->count > 0)
-      hipLaunchKernelGGL((ts_tn_zsum_kernel<4>), grid, dim3(256), 0, stream, A, n, rows_per_chunk,
-                         partial, cond, *zs);
-    else
-      hipLaunchKernelGGL((ts_tn_stream_lds_kernel<4>), grid, dim3(256), 0, stream, A, B.blk[0],
-                         n, rows_per_chunk, partial, cond);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_reduce(partial, nchunks, elems, out, cond, stream);
-  }
-  if (zs && zs->count > 0) return hipErrorNotSupported;  // the Z sums: streaming form only
-  if (B.count == 1 && B.width == 8 && A.width == 8) {
+    if ((size_t)(s_chunks * ca * cb) <= partial_elems && s_rows <= TS_MAX_CHUNK && s_chunks > 0) {
+      plan->form = TN_FORM_STREAM;
+      plan->nchunks = s_chunks;
+      plan->rows_per_chunk = s_rows;
+      return hipSuccess;
+    }
     // line form: ~2048 waves, >= 64 rows per chunk, partials within the buffer
-    const int64_t elems = (int64_t)ca * cb;
-    const int groups = (A.count + 7) / 8;
+    const int groups = (a_count + 7) / 8;
     int64_t nchunks = 2048 / groups;
     if (nchunks < 1) nchunks = 1;
     if (nchunks > (n + 63) / 64) nchunks = (n + 63) / 64;
@@ -698,23 +690,67 @@ static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n
     if (nchunks < 1) return hipErrorInvalidValue;
     int64_t rows_per_chunk = (n + nchunks - 1) / nchunks;
     rows_per_chunk = (rows_per_chunk + 15) & ~(int64_t)15;
-    nchunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-    const dim3 grid((unsigned)nchunks, (unsigned)((groups + 3) / 4));
-    hipLaunchKernelGGL(ts_tn_lines_kernel, grid, dim3(256), 0, stream, A, B.blk[0], n,
-                       rows_per_chunk, partial, cond);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_reduce(partial, nchunks, elems, out, cond, stream);
+    plan->form = TN_FORM_LINES;
+    plan->nchunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    plan->rows_per_chunk = rows_per_chunk;
+    return hipSuccess;
   }
-  if (B.count == 1 && (B.width == 8 || B.width == 16) && A.width % 4 == 0) {
+  if (b_count == 1 && (b_width == 8 || b_width == 16) && a_width % 4 == 0) {
     // narrow form: ~1024 workgroups of >= 256 rows, partials within the buffer
-    const int64_t elems = (int64_t)ca * cb;
     int64_t nchunks = (n + 255) / 256;
     if (nchunks > 1024) nchunks = 1024;
     if ((size_t)(nchunks * elems) > partial_elems) nchunks = (int64_t)(partial_elems / elems);
     if (nchunks < 1) return hipErrorInvalidValue;
     const int64_t rows_per_chunk = (n + nchunks - 1) / nchunks;
-    nchunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    plan->form = TN_FORM_NARROW;
+    plan->nchunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    plan->rows_per_chunk = rows_per_chunk;
+    plan->flush = rows_per_chunk / 4 > TN_FLUSH ? 1 : 0;  // rows per wave beyond one fp32 span
+    return hipSuccess;
+  }
+  const int nti = (ca + 31) / 32, ntj = (cb + 31) / 32;
+  const int ntiles = nti * ntj;
+  // chunk count: ~1024 workgroups with >= 512 rows per chunk, partials within the buffer
+  int64_t nchunks = (n + 511) / 512;
+  int64_t cap = 1024 / ntiles;
+  if (cap < 1) cap = 1;
+  if (nchunks > cap) nchunks = cap;
+  if ((size_t)(nchunks * elems) > partial_elems) nchunks = (int64_t)(partial_elems / elems);
+  if (nchunks < 1) return hipErrorInvalidValue;
+  int64_t rows_per_chunk = (n + nchunks - 1) / nchunks;
+  rows_per_chunk = (rows_per_chunk + 7) & ~(int64_t)7;
+  plan->form = TN_FORM_MFMA;
+  plan->nchunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+  plan->rows_per_chunk = rows_per_chunk;
+  return hipSuccess;
+}
+
+static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n,
+                               double* partial, size_t partial_elems, double* out,
+                               const int* cond, const ZSum* zs, hipStream_t stream) {
+  const int ca = A.count * A.width, cb = B.count * B.width;
+  const int64_t elems = (int64_t)ca * cb;
+  TnPlan plan{};
+  const hipError_t pe = n2v2r_ts_tn_plan(A.count, A.width, B.count, B.width, n, partial_elems, &plan);
+  const bool zsum = zs && zs->count > 0;
+  // the Z sums: streaming form only
+  if (zsum && (pe != hipSuccess || plan.form != TN_FORM_STREAM)) return hipErrorNotSupported;
+  if (pe != hipSuccess) return pe;
+  const int64_t nchunks = plan.nchunks, rows_per_chunk = plan.rows_per_chunk;
+  if (plan.form == TN_FORM_STREAM) {
+    const dim3 grid((unsigned)nchunks, (unsigned)((A.count + 3) / 4));
+    if (zsum)
+      hipLaunchKernelGGL((ts_tn_zsum_kernel<4>), grid, dim3(256), 0, stream, A, n, rows_per_chunk,
+                         partial, cond, *zs);
+    else
+      hipLaunchKernelGGL((ts_tn_stream_lds_kernel<4>), grid, dim3(256), 0, stream, A, B.blk[0],
+                         n, rows_per_chunk, partial, cond);
+  } else if (plan.form == TN_FORM_LINES) {
+    const int groups = (A.count + 7) / 8;
+    const dim3 grid((unsigned)nchunks, (unsigned)((groups + 3) / 4));
+    hipLaunchKernelGGL(ts_tn_lines_kernel, grid, dim3(256), 0, stream, A, B.blk[0], n,
+                       rows_per_chunk, partial, cond);
+  } else if (plan.form == TN_FORM_NARROW) {
     const int groups = (ca + 255) / 256;
     const size_t lds = sizeof(double) * 4 * 256 * B.width;
     const dim3 grid((unsigned)nchunks, (unsigned)groups);
@@ -727,7 +763,7 @@ static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n
       (void)hipGetLastError();  // a refused attribute must not surface at a later launch
       attr = true;
     }
-    const bool flush = rows_per_chunk / 4 > TN_FLUSH;  // rows per wave beyond one fp32 span
+    const bool flush = plan.flush != 0;
 #define TN_NARROW(J, F)                                                                    \
   hipLaunchKernelGGL((ts_tn_narrow_kernel<J, F>), grid, dim3(256), lds, stream, A, B.blk[0], n, \
                      rows_per_chunk, partial, cond)
@@ -737,26 +773,12 @@ static hipError_t launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n
       if (flush) TN_NARROW(16, true); else TN_NARROW(16, false);
     }
 #undef TN_NARROW
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_reduce(partial, nchunks, elems, out, cond, stream);
+  } else {
+    const int nti = (ca + 31) / 32, ntj = (cb + 31) / 32;
+    dim3 grid((unsigned)nchunks, (unsigned)(nti * ntj));
+    hipLaunchKernelGGL(ts_tn_kernel, grid, dim3(256), 0, stream, A, B, n, rows_per_chunk, ntj,
+                       partial, cond);
   }
-  const int nti = (ca + 31) / 32, ntj = (cb + 31) / 32;
-  const int ntiles = nti * ntj;
-  // chunk count: ~1024 workgroups with >= 512 rows per chunk, partials within the buffer
-  int64_t nchunks = (n + 511) / 512;
-  int64_t cap = 1024 / ntiles;
-  if (cap < 1) cap = 1;
-  if (nchunks > cap) nchunks = cap;
-  const int64_t elems = (int64_t)ca * cb;
-  if ((size_t)(nchunks * elems) > partial_elems) nchunks = (int64_t)(partial_elems / elems);
-  if (nchunks < 1) return hipErrorInvalidValue;
-  int64_t rows_per_chunk = (n + nchunks - 1) / nchunks;
-  rows_per_chunk = (rows_per_chunk + 7) & ~(int64_t)7;
-  nchunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  dim3 grid((unsigned)nchunks, (unsigned)ntiles);
-  hipLaunchKernelGGL(ts_tn_kernel, grid, dim3(256), 0, stream, A, B, n, rows_per_chunk, ntj,
-                     partial, cond);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_reduce(partial, nchunks, elems, out, cond, stream);
@@ -1112,6 +1134,12 @@ __global__ __launch_bounds__(NN_T) void ts_nn_kernel(BlockList A, Coef F, int cb
   const int64_t lrow = row_ok ? row : (n > 0 ? n - 1 : 0);
   const bool vec4 = F.G && (F.ldg % 4) == 0 && (cb % 4) == 0 &&
                     (reinterpret_cast<uintptr_t>(F.G) & 15) == 0;
+  // flags (the orthogonalisation apply: A's last block is the block being replaced, cb wide): a
+  // flagged column of it may hold non-finite values; its coefficients are zero, so it is read
+  // as zeros (0 x NaN would spread to every output column of the row)
+  const int zc0 = ca - cb;
+  const unsigned long long zmask =
+      (flags && cb <= 64) ? __ballot(lane < cb && flags[lane < cb ? lane : 0] != 0) : 0ull;
   for (int k0 = 0; k0 < ca; k0 += NN_KCH) {
     const int kn = (ca - k0) < NN_KCH ? (ca - k0) : NN_KCH;
     f32x4 a4[NN_KCH / 8];
@@ -1149,6 +1177,15 @@ __global__ __launch_bounds__(NN_T) void ts_nn_kernel(BlockList A, Coef F, int cb
       }
     }
     __syncthreads();
+    if (zmask != 0ull && k0 + kn > zc0) {  // (uniform; rare)
+#pragma unroll
+      for (int s8 = 0; s8 < NN_KCH / 8; ++s8) {
+        const int jz = k0 + 8 * s8 + 4 * h - zc0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+          if (8 * s8 < kn && jz >= 0 && ((zmask >> (jz + m)) & 1ull)) a4[s8][m] = 0.f;
+      }
+    }
 #pragma unroll
     for (int s8 = 0; s8 < NN_KCH / 8; ++s8) {
       if (8 * s8 >= kn) break;
@@ -1358,6 +1395,12 @@ __global__ __launch_bounds__(256) void ts_nn_rows_kernel(BlockList A, Coef F, in
 #pragma unroll
   for (int j = 0; j < CB; ++j) acc[j] = 0.f;
   const int w = A.width;
+  // flags (the orthogonalisation apply: A's last block is the block being replaced, cb wide): a
+  // flagged column of it may hold non-finite values; its coefficients are zero, so it is read
+  // as zeros (0 x NaN would spread to every output column of the row)
+  unsigned zmask = 0;
+  if (flags && w == cb)
+    for (int j = 0; j < cb; ++j) zmask |= flags[j] ? 1u << j : 0u;
   int q = 0;
   if (w == CB) {  // Krylov blocks: 4 blocks (4 x CB/4 16-B loads) in flight per step
     constexpr int NL = CB / 4;
@@ -1368,6 +1411,13 @@ __global__ __launch_bounds__(256) void ts_nn_rows_kernel(BlockList A, Coef F, in
 #pragma unroll
         for (int l = 0; l < NL; ++l)
           a4[u][l] = *reinterpret_cast<const f32x4*>(A.blk[q + u] + row * (int64_t)CB + 4 * l);
+      if (zmask && q + 4 == A.count) {  // (uniform; rare)
+#pragma unroll
+        for (int l = 0; l < NL; ++l)
+#pragma unroll
+          for (int m = 0; m < 4; ++m)
+            if ((zmask >> (4 * l + m)) & 1u) a4[3][l][m] = 0.f;
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -1383,7 +1433,12 @@ __global__ __launch_bounds__(256) void ts_nn_rows_kernel(BlockList A, Coef F, in
   for (; q < A.count; ++q) {
     const float* ap = A.blk[q] + row * (int64_t)w;
     for (int kk = 0; kk < w; kk += 4) {
-      const f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + kk);
+      f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + kk);
+      if (zmask && q + 1 == A.count) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+          if ((zmask >> (kk + m)) & 1u) a4[m] = 0.f;
+      }
       const float* g = gs + (q * w + kk) * CB;
 #pragma unroll
       for (int m = 0; m < 4; ++m)
@@ -1401,25 +1456,38 @@ __global__ __launch_bounds__(256) void ts_nn_rows_kernel(BlockList A, Coef F, in
   }
 }
 
+// Which product kernel launch_nn takes for A (a_count blocks of a_width) and cb output columns
+// (the launcher's rule; the diagnostic entries report it): 8 / 16 = ts_nn_rows_kernel<8> / <16>
+// (F within 64 KB of LDS), 32 NT = ts_nn_kernel<NT>, -1 = a shape it refuses.
+extern "C" int n2v2r_nn_kernel(int a_count, int a_width, int cb) {
+  if ((a_count * a_width) % 8 != 0 || a_width % 8 != 0) return -1;
+  const size_t lds8 = sizeof(float) * (size_t)a_count * a_width * 8;
+  if (cb <= 8 && lds8 <= 64 * 1024) return 8;
+  if (cb <= 16 && 2 * lds8 <= 64 * 1024) return 16;
+  const int nt = (cb + 31) / 32;
+  return nt >= 1 && nt <= 4 ? 32 * nt : -1;
+}
+
 static hipError_t launch_nn(const BlockList& A, const Coef& F, int cb, const OutBlockList& O,
                             const BlockList& C, float alpha, float beta, int64_t n,
                             const int* cond, const int* flags, uint64_t seed, int64_t row0,
                             hipStream_t stream) {
-  if ((A.count * A.width) % 8 != 0 || A.width % 8 != 0) return hipErrorInvalidValue;
+  const int kern = n2v2r_nn_kernel(A.count, A.width, cb);
+  if (kern < 0) return hipErrorInvalidValue;
   const size_t lds8 = sizeof(float) * (size_t)A.count * A.width * 8;
   const size_t lds16 = 2 * lds8;
-  if (cb <= 8 && lds8 <= 64 * 1024) {
+  if (kern == 8) {
     hipLaunchKernelGGL(ts_nn_rows_kernel<8>, dim3((unsigned)((n + 255) / 256)), dim3(256), lds8,
                        stream, A, F, cb, O, C, alpha, beta, n, cond, flags, seed, row0);
     return hipGetLastError();
   }
-  if (cb <= 16 && lds16 <= 64 * 1024) {
+  if (kern == 16) {
     hipLaunchKernelGGL(ts_nn_rows_kernel<16>, dim3((unsigned)((n + 255) / 256)), dim3(256), lds16,
                        stream, A, F, cb, O, C, alpha, beta, n, cond, flags, seed, row0);
     return hipGetLastError();
   }
   dim3 grid((unsigned)((n + 32 * NN_WAVES - 1) / (32 * NN_WAVES)));
-  switch ((cb + 31) / 32) {
+  switch (kern / 32) {
     case 1: hipLaunchKernelGGL(ts_nn_kernel<1>, grid, dim3(NN_T), 0, stream, A, F, cb, O, C, alpha, beta, n, cond, flags, seed, row0); break;
     case 2: hipLaunchKernelGGL(ts_nn_kernel<2>, grid, dim3(NN_T), 0, stream, A, F, cb, O, C, alpha, beta, n, cond, flags, seed, row0); break;
     case 3: hipLaunchKernelGGL(ts_nn_kernel<3>, grid, dim3(NN_T), 0, stream, A, F, cb, O, C, alpha, beta, n, cond, flags, seed, row0); break;
@@ -1637,7 +1705,9 @@ __global__ __launch_bounds__(1024) void pip_chol_kernel(const double* __restrict
         X[j][ej] = x;
       }
       __syncthreads();
-      if (own && ei < j) x -= R[ei][j] * X[j][ej];
+      // (a flagged column's entries above the diagonal count as zero: they may be non-finite,
+      // and row j of X is the unit row, so they would reach only the column that is dropped)
+      if (own && ei < j && !bad[j]) x -= R[ei][j] * X[j][ej];
     }
   } else if (tid < 64) {
     // O(b^3), b <= 64: wave 0 alone, synchronised as a wave (LDS executes a wave's accesses in
@@ -1678,6 +1748,7 @@ __global__ __launch_bounds__(1024) void pip_chol_kernel(const double* __restrict
       const double inv = 1.0 / R[j][j];
       for (int cc = tid; cc < b; cc += nw) X[j][cc] *= inv;
       PIP_WSYNC();
+      if (bad[j]) continue;  // (its entries above the diagonal count as zero: see above)
       for (int e = tid; e < j * b; e += nw) {
         const int r = e / b, cc = e % b;
         X[r][cc] -= R[r][j] * X[j][cc];
@@ -1724,7 +1795,8 @@ __global__ __launch_bounds__(1024) void pip_chol_kernel(const double* __restrict
         float v = 0.f;
         if (!bad[j]) {
           double sacc = 0.0;
-          for (int m = 0; m <= j; ++m) sacc -= cst[kk * b + m] * X[m][j];
+          // (a flagged column m of C may be non-finite; X[m][j] is zero)
+          for (int m = 0; m <= j; ++m) sacc -= (bad[m] ? 0.0 : cst[kk * b + m]) * X[m][j];
           v = (float)sacc;
         }
         fout[(int64_t)k0 * b + e] = v;
@@ -1745,7 +1817,7 @@ __global__ __launch_bounds__(1024) void pip_chol_kernel(const double* __restrict
         } else {
           const double* crow = Gs + (int64_t)k * b;
           double sacc = 0.0;
-          for (int m = 0; m <= j; ++m) sacc -= crow[m] * X[m][j];
+          for (int m = 0; m <= j; ++m) sacc -= (bad[m] ? 0.0 : crow[m]) * X[m][j];
           v = (float)sacc;
         }
       }
@@ -1754,13 +1826,21 @@ __global__ __launch_bounds__(1024) void pip_chol_kernel(const double* __restrict
   }
 }
 
+// pip_chol's launch shape (the launcher's rule; the diagnostic entries report it).  stage: G goes
+// through LDS while (c + b) b fp64 fit 56 KB.  nwg: wide blocks with F wanted spread F's rows
+// over up to 8 workgroups (each factors P itself).
+extern "C" void n2v2r_pip_chol_plan(int c, int b, int with_f, int* stage, int* nwg) {
+  const size_t gbytes = sizeof(double) * (size_t)(c + b) * b;
+  *stage = gbytes <= 56 * 1024 ? 1 : 0;
+  *nwg = (with_f && b > 8) ? std::min(8, (c + b + 127) / 128) : 1;
+}
+
 extern "C" hipError_t n2v2r_launch_pip_chol(const double* G, int c, int b, double* xinv,
                                             float* fout, const PipPass& p, hipStream_t stream) {
   if (b > 64) return hipErrorInvalidValue;
   const size_t gbytes = sizeof(double) * (size_t)(c + b) * b;
-  const int stage = gbytes <= 56 * 1024 ? 1 : 0;
-  // wide blocks with F wanted: F's rows over up to 8 workgroups (each factors P itself)
-  const int nwg = (fout && b > 8) ? std::min(8, (c + b + 127) / 128) : 1;
+  int stage = 0, nwg = 1;
+  n2v2r_pip_chol_plan(c, b, fout != nullptr, &stage, &nwg);
   hipLaunchKernelGGL(pip_chol_kernel, dim3(nwg), dim3(1024), stage ? gbytes : 0, stream, G, c, b,
                      xinv, p.flags, p.any_flag, p.cond, p.save, p.save_row0, p.save_rows, fout,
                      stage, p.sticky, p.rsave, p.first);

@@ -27,7 +27,21 @@ struct PipPass {
                               // resolve is clamped and the column kept; later passes refill it
 };
 
+// The Gram launcher's decision for a shape (n2v2r_ts_tn_plan): which kernel, over how many row
+// chunks, and for the narrow form whether the instantiation that flushes its fp32 sums ran.
+enum { TN_FORM_STREAM = 0, TN_FORM_LINES = 1, TN_FORM_NARROW = 2, TN_FORM_MFMA = 3 };
+struct TnPlan {
+  int form;
+  int flush;
+  int64_t nchunks, rows_per_chunk;
+};
+
 extern "C" {
+// The launchers' shape decisions as pure functions; each launcher calls its own.
+hipError_t n2v2r_ts_tn_plan(int a_count, int a_width, int b_count, int b_width, int64_t n,
+                            size_t partial_elems, TnPlan* plan);
+void n2v2r_pip_chol_plan(int c, int b, int with_f, int* stage, int* nwg);
+int n2v2r_nn_kernel(int a_count, int a_width, int cb);
 hipError_t n2v2r_launch_ts_tn(const BlockList& A, const BlockList& B, int64_t n, double* partial,
                               size_t partial_elems, double* out, const int* cond,
                               hipStream_t stream);

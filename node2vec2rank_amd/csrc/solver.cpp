@@ -707,7 +707,8 @@ struct Eig {
   // flg_p + 64 s, any-flag at any_p + s.  any_p + 3 is the cycle's sticky flag.
 
   // the refill seed of the next pass: one per pass, in launch order
-  uint64_t next_fill_seed() { return seed ^ (0xABCDull + ++fill_counter); }
+  uint64_t last_fill_seed = 0;  // (diagnostics)
+  uint64_t next_fill_seed() { return last_fill_seed = seed ^ (0xABCDull + ++fill_counter); }
 
   PipPass pass_in_slot(int s) const {
     PipPass p;
@@ -2072,6 +2073,145 @@ int n2v2r_ritz_step(n2v2r_handle* h, int b, int nq, int keep, int lean, const fl
       info->fused = eig.ritz_done ? 1 : 0;
       info->launches = eig.ritz_launches;
       info->lds_bytes = eig.ritz_done ? (int)n2v2r_ritz_nn_lds_bytes(nq, keep) : 0;
+    }
+    return N2V2R_OK;
+  });
+}
+
+// An Eig set up as a fit's whose plan is block width b and a basis of nblk blocks (the Gram and
+// pass diagnostics below); 0, or the status to return.
+static int diag_eig(n2v2r_handle* h, int b, int nblk, Eig& eig) {
+  if (h->multi() || h->comm || (b != 8 && b != 16 && b != 32 && b != 64) || nblk < 1 ||
+      (int64_t)nblk * b > N2V2R_BAND_MAXC)
+    return N2V2R_ERR_BAD_ARG;
+  if (h->K < 1) {
+    h->err = "no layers set";
+    return N2V2R_ERR_BAD_ARG;
+  }
+  for (auto& L : h->layers)
+    if (!L->loaded) {
+      h->err = "a layer was not loaded";
+      return N2V2R_ERR_BAD_ARG;
+    }
+  eig.h = h;
+  eig.st = h->stream;
+  eig.n = h->nloc;
+  eig.npad = h->npad;
+  eig.row0 = h->row0;
+  eig.K = h->K;
+  eig.b = b;
+  eig.keep = b;
+  eig.pb = 1;
+  eig.nb_max = nblk;
+  eig.c_max = nblk * b;
+  eig.stats = nullptr;
+  eig.reuse_pool();
+  eig.size_scratch();
+  return N2V2R_OK;
+}
+
+// the Gram launcher's plan for [na blocks]^T [nb blocks] on this Eig's partial buffer
+static int diag_gram_info(const Eig& eig, int na, int nb, n2v2r_pass_info* info) {
+  TnPlan plan{};
+  if (n2v2r_ts_tn_plan(na, eig.b, nb, eig.b, eig.n, eig.part_n, &plan) != hipSuccess)
+    return N2V2R_ERR_BAD_ARG;
+  if (info) {
+    *info = n2v2r_pass_info{};
+    info->gram_form = plan.form;
+    info->gram_flush = plan.flush;
+    info->nchunks = plan.nchunks;
+    info->rows_per_chunk = plan.rows_per_chunk;
+  }
+  return N2V2R_OK;
+}
+
+// One Gram alone (tests): an Eig set up as a fit's with the given plan, its tn on host blocks.
+int n2v2r_block_gram(n2v2r_handle* h, int b, int na, int nb, const float* A, const float* B,
+                     double* G, n2v2r_pass_info* info) {
+  return guarded(h, [&]() -> int {
+    if (na < 1 || nb < 1 || !A || !B || !G) return N2V2R_ERR_BAD_ARG;
+    Eig eig{};
+    if (const int s = diag_eig(h, b, std::max(na, nb), eig)) return s;
+    if (const int s = diag_gram_info(eig, na, nb, info)) return s;
+    hipStream_t st = eig.st;
+    const size_t rows = sizeof(float) * (size_t)eig.n * b;
+    std::vector<float*> a, bb;
+    for (int q = 0; q < na; ++q) {
+      a.push_back(eig.take());
+      HIPCHK(hipMemcpyAsync(a[q], A + (size_t)q * eig.n * b, rows, hipMemcpyHostToDevice, st));
+    }
+    for (int q = 0; q < nb; ++q) {
+      bb.push_back(eig.take());
+      HIPCHK(hipMemcpyAsync(bb[q], B + (size_t)q * eig.n * b, rows, hipMemcpyHostToDevice, st));
+    }
+    // NaN bytes in the Gram and in every chunk partial the launch has to write
+    const size_t gbytes = sizeof(double) * (size_t)na * b * nb * b;
+    HIPCHK(hipMemsetAsync(eig.gsm_p, 0xFF, gbytes, st));
+    HIPCHK(hipMemsetAsync(eig.part_p, 0xFF, h->partial.bytes, st));
+    HIPCHK(hipStreamSynchronize(st));  // pageable sources: complete before the kernels
+    eig.tn(eig.blocks(a, 0, na), eig.blocks(bb, 0, nb), eig.gsm_p, nullptr);
+    HIPCHK(hipMemcpyAsync(G, eig.gsm_p, gbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return N2V2R_OK;
+  });
+}
+
+// One orthogonalisation pass alone (tests): an Eig set up as a fit's with the given plan, its
+// pip_pass on host blocks.
+int n2v2r_ortho_pass(n2v2r_handle* h, int b, int nq, const float* Q, float* Z, int in_place,
+                     int first, int cond, uint64_t seed, double* gram, double* xinv, float* F,
+                     int* flags, int* any_flag, n2v2r_pass_info* info) {
+  return guarded(h, [&]() -> int {
+    if (nq < 0 || (nq > 0 && !Q) || !Z || !gram || !flags || !any_flag || cond < -1 || cond > 1 ||
+        (b != 8 && (!xinv || !F)))
+      return N2V2R_ERR_BAD_ARG;
+    Eig eig{};
+    if (const int s = diag_eig(h, b, nq + 1, eig)) return s;
+    if (const int s = diag_gram_info(eig, nq + 1, 1, info)) return s;
+    const int c = nq * b;
+    const int kern = b == 8 ? 0 : n2v2r_nn_kernel(nq + 1, b, b);
+    if (kern < 0) return N2V2R_ERR_BAD_ARG;
+    eig.seed = seed;
+    hipStream_t st = eig.st;
+    const size_t rows = sizeof(float) * (size_t)eig.n * b;
+    std::vector<float*> basis;
+    for (int q = 0; q < nq; ++q) {
+      basis.push_back(eig.take());
+      HIPCHK(hipMemcpyAsync(basis[q], Q + (size_t)q * eig.n * b, rows, hipMemcpyHostToDevice, st));
+    }
+    float* zin = eig.take();
+    float* z = in_place ? zin : eig.take();
+    HIPCHK(hipMemcpyAsync(zin, Z, rows, hipMemcpyHostToDevice, st));
+    // NaN bytes wherever the pass has to write, a non-zero pattern in the flag words
+    if (!in_place) HIPCHK(hipMemsetAsync(z, 0xFF, rows, st));
+    const size_t gbytes = sizeof(double) * (size_t)(c + b) * b;
+    HIPCHK(hipMemsetAsync(eig.gsm_p, 0xFF, gbytes, st));
+    HIPCHK(hipMemsetAsync(eig.part_p, 0xFF, h->partial.bytes, st));
+    HIPCHK(hipMemsetAsync(h->ews.rinv.p, 0xFF, h->ews.rinv.bytes, st));
+    HIPCHK(hipMemsetAsync(h->ews.fcoef.p, 0xFF, h->ews.fcoef.bytes, st));
+    HIPCHK(hipMemsetAsync(eig.flg_p, 0x5A, sizeof(int) * 256, st));
+    HIPCHK(hipMemsetAsync(eig.any_p, 0x5A, sizeof(int) * 4, st));
+    // the pass's slot as the solver gives it: first (0), full (1), or the conditional third (2)
+    PipPass p = cond >= 0 ? eig.third_pass() : eig.pass_in_slot(first ? 0 : 1);
+    p.first = first;
+    if (cond >= 0)
+      HIPCHK(hipMemcpyAsync(const_cast<int*>(p.cond), &cond, sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // pageable sources: complete before the kernels
+    eig.pip_pass(z, basis, p, in_place ? nullptr : zin);
+    HIPCHK(hipMemcpyAsync(Z, z, rows, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(gram, eig.gsm_p, gbytes, hipMemcpyDeviceToHost, st));
+    if (b != 8) {
+      HIPCHK(hipMemcpyAsync(xinv, h->ews.rinv.p, sizeof(double) * b * b, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(F, h->ews.fcoef.p, sizeof(float) * (size_t)(c + b) * b,
+                            hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipMemcpyAsync(flags, p.flags, sizeof(int) * b, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(any_flag, p.any_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (info) {
+      if (b != 8) n2v2r_pip_chol_plan(c, b, 1, &info->stage, &info->nwg);
+      info->apply_kernel = kern;
+      info->fill_seed = eig.last_fill_seed;
     }
     return N2V2R_OK;
   });
