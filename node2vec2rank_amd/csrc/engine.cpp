@@ -1,7 +1,8 @@
 // n2v2r engine: handle lifecycle and the diagnostic entry points (include/n2v2r_diag.h).
-// The rest of the C-ABI: layers.cpp (ingest), solver.cpp (UASE), ranking.cpp (distances,
-// Borda), comm.cpp (row-partitioned communicators), multi.cpp (one process, N GPUs).
-#include "engine.h"
+// The rest of the C-ABI: layers.cpp (ingest), solver.cpp (UASE), gram_op.cpp (the Gram operator),
+// ranking.cpp (distances, Borda), comm.cpp (row-partitioned communicators), multi.cpp (one
+// process, N GPUs).
+#include "gram_op.h"
 
 using namespace n2v2r_int;
 
@@ -267,32 +268,19 @@ int n2v2r_spmm_col_blocks(const n2v2r_handle* h, int b) {
 // launches after a warm-up.  N2V2R_ERR_BAD_ARG when the layer cannot take packed blocks.
 static int time_tiled(n2v2r_handle* h, int k, int transpose, int nb, const float* xd, float* yd,
                       int reps, double* avg_ms) {
-  if (nb <= 0) {
-    nb = 4;
-    while (nb < 64 && (double)h->n * 32.0 / nb > 2.0 * 1024 * 1024) nb *= 2;
-  }
+  if (nb <= 0) nb = tile_nb_auto(h->n);
   if (nb != 4 && nb != 8 && nb != 16 && nb != 32 && nb != 64 && nb != 128) return N2V2R_ERR_BAD_ARG;
   LayerDev& L = *h->layers[k];
   const int wb = tile_wbits(h->layers, nb);
   if (!ensure_col_blocks(L, h->n, h->stream, nb, wb)) return N2V2R_ERR_BAD_ARG;
   const LayerDev::ColBlocks& cbs = (transpose && !L.symmetric) ? L.cb_t : L.cb;
-  DevBuf tb;
+  DevBuf tb;  // this layer's blocks alone
   tb.ensure(sizeof(CsrBlk) * nb);
   HIPCHK(hipMemcpyAsync(tb.p, cbs.blk, sizeof(CsrBlk) * nb, hipMemcpyHostToDevice, h->stream));
-  int ncu = 0;
-  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
-  SpmmTileArgs a{};
-  a.blk = tb.as<CsrBlk>();
+  SpmmTileArgs a =
+      spmm_tile_args(tb.as<CsrBlk>(), nb, wb, tile_rows_for(h, wb), h->nloc, 0, 1, 0, 8);
   a.X[0] = xd;
   a.Y[0] = yd;
-  a.ldx = 8;
-  a.ldy = 8;
-  a.n = h->nloc;
-  a.K = 1;
-  a.nb = nb;
-  a.sum = 0;
-  a.tile_rows = n2v2r_spmm_tile_rows(h->nloc, ncu, 2, wb);
-  a.wbits = wb;
   HIPCHK(n2v2r_launch_spmm_tile(a, h->stream));  // warm-up
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));

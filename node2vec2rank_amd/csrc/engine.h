@@ -1,6 +1,7 @@
-// Internal declarations shared by the engine's host sources (solver.cpp, layers.cpp,
+// Internal declarations shared by the engine's host sources (solver.cpp, gram_op.cpp, layers.cpp,
 // ranking.cpp, comm.cpp, multi.cpp, engine.cpp): the kernel launchers, device buffers, layer
-// storage, communicators and the handle.  Not part of the C-ABI (include/n2v2r.h).
+// storage, communicators and the handle.  The Gram operator built on them is gram_op.h.  Not
+// part of the C-ABI (include/n2v2r.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -741,8 +742,6 @@ inline double spmm_algo_bytes(int64_t nnz, bool unit, int64_t rows, int64_t pane
          4.0 * (double)(panel_rows + rows) * b;
 }
 
-// the tiled column-block SpMM wanted at panel width b (solver.cpp)
-bool col_blocks_wanted(const n2v2r_handle* h, int b);
 // the launches of a pair's two selective passes after its Gram (solver.cpp: Eig::pair_pass and
 // the diagnostic n2v2r_pip_pass).  all: Q's blocks, then Za, then Zb; pa.rsave: R of Za's pass;
 // plan: the paired apply's plan buffer, or nullptr for the three-launch form.  true: the paired

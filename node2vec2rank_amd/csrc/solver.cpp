@@ -22,36 +22,13 @@
 // + an all-reduce, so every rank holds identical small matrices and runs the identical host
 // Rayleigh-Ritz.  Communicators: RCCL (one process per GPU) or an in-process thread group
 // (W ranks on one GPU, for testing the partitioned algorithm without W devices).
-#include "engine.h"
+#include "gram_op.h"
 
 #include <optional>
 
 using namespace n2v2r_int;
 
 namespace n2v2r_int {
-// The column-block SpMM (the flat-window tiled form): b = 8 CSR panels beyond 8 MB (beyond one
-// XCD's L2); N2V2R_SPMM_CB=1 / 0 forces it on / off (tests, A/B runs).
-// Read on every call, so a test can switch it between fits.
-bool col_blocks_wanted(const n2v2r_handle* h, int b);
-
-// Partitioned handles: the stage-1 panel Z_k of each layer all-gathered on a stream of its own
-// while the next layer's stage 1 runs, unless N2V2R_GATHER_OVERLAP=0.  Read per call.
-bool gather_overlap() {
-  const char* e = std::getenv("N2V2R_GATHER_OVERLAP");
-  return !(e && e[0] == '0');
-}
-
-// XCD-split second SpMM stage: b = 8 CSR layers on one GPU whose K stage-2 panels together
-// exceed an XCD's 4 MB L2 (cfg2: 33.5 -> 24 us per stage; at N = 30k, where both panels fit,
-// 4 % slower).  N2V2R_SPMM_SPLIT=1 / 0 forces it on / off.
-bool split2_wanted(const n2v2r_handle* h, int b) {
-  const char* e = std::getenv("N2V2R_SPMM_SPLIT");  // read per fit (tests flip it)
-  const int force = e ? (e[0] == '0' ? 0 : 1) : -1;
-  if (b != 8 || h->comm || h->dense_layers() || h->K < 2 || h->K > 8) return false;
-  if (force >= 0) return force == 1;
-  return (double)h->K * (double)h->n * 32.0 > 4.0 * 1024 * 1024;
-}
-
 // The default basis cap of the b = 8 banded fits: 640 columns, N2V2R_BAND_MAXC = 768 for graphs
 // from 4M nodes (round 6: the fused PIP pass past 64 KB of LDS; at cfg4's 1M nodes 768 columns
 // are no better -- 771 block applications against 788 on one graph, 846 against 788 on the
@@ -201,46 +178,26 @@ struct Eig {
   int64_t npad;     // local rows incl. padding (panel allocation)
   int64_t row0;     // global index of local row 0
   int K;
-  int b;            // block width
-  int nb_max;       // max basis blocks
-  int pb;           // kept blocks at restart
-  int d;
-  uint64_t seed;
+  GramOp op;        // W = M X in the fit's form
+  int b = 0;        // block width
+  int nb_max = 0;   // max basis blocks
+  int pb = 0;       // kept blocks at restart
+  int d = 0;
+  uint64_t seed = 0;
   std::vector<float*> freelist;
   std::vector<float*> Q, W;                   // current basis / images
-  n2v2r_eig_stats* stats;
-  double t_spmm = 0, t_ortho = 0;
-  int64_t launches = 0;
-  double algo_bytes = 0;
+  n2v2r_eig_stats* stats = nullptr;
+  double t_ortho = 0;
   uint64_t fill_counter = 0;
   int kry0 = 0;             // index of the first Krylov block of the current cycle
   bool full_first = false;  // N2V2R_EIG_FULL_FIRST_PASS
   bool band_rr = false;     // banded Rayleigh-Ritz (b = 8, c <= 640), else dense
   bool band_reduce = false; // the reducing banded path takes the cycle (keep + 8 <= 192, c <= 640)
-  // the flat-window tiled column-block SpMM (b = 8, panels beyond 8 MB): row tiles with LDS
-  // accumulators walking tile_nb column-block phases, one launch per stage
-  bool col_blocks = false;
   // the final lean check's stage-1 products Z_k = A_k^T X[q] of the d wanted Ritz vectors, kept
   // in the embedding buffer (h->Y, unscaled): they ARE the embedding's A_k^T U before the sign
   // and sigma^-1/2 column scaling -- the same tiled launch, the same summation order -- so the
   // embedding step skips its d/8 SpMM launches (cfg4: 16 x 0.74 ms)
   bool y_captured = false;
-  int tile_rows = 0, tile_nb = CB_NB, tile_wb = CB_WIN_BITS_MIN;
-  // partitioned CSR handles: stage 2 as a reduce-scatter of this rank's column share (default
-  // at W > 1) instead of all-gathers of every layer's stage-1 panel (N2V2R_DIST_STAGE2=gather)
-  bool rs_form = false;
-  // reduce-scatter form: stage 2 in rs_chunks row chunks of rs_rc local rows, each chunk's
-  // reduce-scatter overlapped with the next chunk's product (N2V2R_RS_CHUNKS, default 4; 1: one
-  // launch and one reduce-scatter)
-  int rs_chunks = 1;
-  int64_t rs_rc = 0;
-  // XCD-split second SpMM stage (b = 8, one GPU): A_k Z_k lands in per-layer partials on the
-  // XCDs of layer k; the image W = sum_k of them is stored by the next Gram pass that reads it
-  // (the local first pass of the next expansion), or by materialize() before any other use
-  bool split2 = false;
-  float* pending = nullptr;  // the W block whose value still sits in the partials
-  // rows per wave of the last row-kernel launch of stage 1 / stage 2 (0: none yet; diagnostics)
-  int rpw1 = 0, rpw2 = 0;
   // the last ritz_vectors: whether the fused kernel made the products, and the product launches
   // (1 fused; else one ts_nn launch per slice and product) (diagnostics)
   bool ritz_done = false;
@@ -270,6 +227,9 @@ struct Eig {
   bool pair_apply = false;  // a pair's two selective passes in one launch (N2V2R_PAIR_APPLY)
   float* deferred = nullptr;
   struct LeanRetry {};
+  // an Eig on a handle, or on one rank of a partitioned one
+  explicit Eig(n2v2r_handle* h_)
+      : h(h_), st(h_->stream), n(h_->nloc), npad(h_->npad), row0(h_->row0), K(h_->K), op(h_) {}
 
   // ---- the fit's plan: what run()'s set-up steps decide and the cycle's steps read ----
   int flags = 0;  // n2v2r_eig_opts.solver_flags
@@ -298,49 +258,6 @@ struct Eig {
   double* gsm_p = nullptr;
   int* flg_p = nullptr;
   int* any_p = nullptr;
-
-  // N2V2R_EIG_TIME_SPMM: an event pair around every SpMM stage launch (h->tev, reused), its
-  // stage (0: A_k^T X, 1: A_k Z_k) and algorithmic bytes; summed after the fit's last sync
-  bool time_spmm = false;
-  std::vector<int> tkind;
-  std::vector<double> tbytes;
-  int tbeg() {
-    if (!time_spmm) return -1;
-    const size_t i = tkind.size();
-    while (h->tev.size() < 2 * (i + 1)) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      h->tev.push_back(e);
-    }
-    HIPCHK(hipEventRecord(h->tev[2 * i], st));
-    tkind.push_back(-1);
-    tbytes.push_back(0.0);
-    return (int)i;
-  }
-  void tend(int i, int kind, double bytes) {
-    if (i < 0) return;
-    HIPCHK(hipEventRecord(h->tev[2 * (size_t)i + 1], st));
-    tkind[i] = kind;
-    tbytes[i] = bytes;
-  }
-  void tsum(n2v2r_eig_stats* out) {
-    if (!time_spmm || !out) return;
-    HIPCHK(hipStreamSynchronize(st));
-    for (size_t i = 0; i < tkind.size(); ++i) {
-      if (tkind[i] < 0) continue;
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, h->tev[2 * i], h->tev[2 * i + 1]));
-      out->gpu_ms_spmm[tkind[i]] += ms;
-      out->spmm_timed_launches[tkind[i]] += 1;
-      out->spmm_stage_bytes[tkind[i]] += tbytes[i];
-    }
-  }
-  double layer_bytes(int k, bool transposed) const {
-    const LayerDev& L = *h->layers[k];
-    const bool t = transposed && !L.symmetric;
-    return spmm_algo_bytes(t ? L.t_nnz : L.nnz, t ? L.t_unit : L.unit, n,
-                           (int64_t)h->world * npad, b);
-  }
 
   // N2V2R_DEBUG_FINITE: stop at the first stage whose output holds a non-finite value
   int dbg_cycle = 0, dbg_apps = 0;
@@ -408,12 +325,7 @@ struct Eig {
                       &h->partial, &h->theta, &h->resid})
       if (d->p) HIPCHK(hipMemsetAsync(d->p, 0xFF, d->bytes, st));
     for (auto& d : w.pool) HIPCHK(hipMemsetAsync(d->p, 0xFF, d->bytes, st));
-    for (auto& d : w.zk) HIPCHK(hipMemsetAsync(d->p, 0xFF, d->bytes, st));
-  }
-
-  // N2V2R_POISON: NaN bytes into every CU's LDS before the next launch
-  void lds_poison() {
-    if (debug_poison()) HIPCHK(n2v2r_launch_lds_poison(st));
+    op.poison_scratch();
   }
 
   float* take() {
@@ -452,254 +364,11 @@ struct Eig {
     return L;
   }
 
-  float* s2part(int k) const { return h->ews.s2part.as<float>() + (size_t)k * npad * 8; }
-  // store the pending image W = sum_k partial_k (fixed layer order)
-  void materialize() {
-    if (!pending) return;
-    const float* parts[8];
-    for (int k = 0; k < K; ++k) parts[k] = s2part(k);
-    HIPCHK(n2v2r_launch_zsum(parts, K, pending, n, st));
-    pending = nullptr;
-  }
-
   // TN over local rows, summed over ranks
   void tn(const BlockList& A, const BlockList& B, double* out, const int* cond) {
     HIPCHK(n2v2r_launch_ts_tn(A, B, n, part_p, part_n, out, cond, st));
     if (h->comm)
       h->allreduce_f64(out, (size_t)A.count * A.width * B.count * B.width);
-  }
-
-  // ---- W = M X: stage 1, Z_k = A_k^T X, and the forms of stage 2, W = sum_k A_k Z_k -------------
-
-  float* zk(int k) const { return h->ews.zk[k]->as<float>(); }
-  // partitioned handles: Z_k all-gathered from every rank (rank-major, global rows)
-  float* gathered_z(int k) const {
-    return h->ews.zg.as<float>() + (size_t)k * h->world * npad * b;
-  }
-  const float* stage2_in(int k) const { return h->comm ? gathered_z(k) : zk(k); }
-  // algorithmic bytes of one stage over all layers (fixed layer order)
-  double stage_bytes(bool transposed) const {
-    double s = 0.0;
-    for (int k = 0; k < K; ++k) s += layer_bytes(k, transposed);
-    return s;
-  }
-
-  // Stage 1 of the CSR forms, one launch: Z_k = A_k^T xg for every layer, or for `layer` alone;
-  // the tiled column-block form when the fit uses it (col_blocks), else the flat one.
-  void stage1(const float* xg, int layer = -1) {
-    const int k0 = layer < 0 ? 0 : layer, nk = layer < 0 ? K : 1;
-    const double bytes = layer < 0 ? stage_bytes(true) : layer_bytes(layer, true);
-    int te;
-    if (col_blocks) {
-      SpmmTileArgs a{};
-      a.blk = h->ews.tblk.as<CsrBlk>() + (size_t)k0 * tile_nb;
-      a.ldx = a.ldy = 8;
-      a.n = n;
-      a.K = nk;
-      a.nb = tile_nb;
-      a.sum = 0;
-      a.tile_rows = tile_rows;
-      a.wbits = tile_wb;
-      for (int i = 0; i < nk; ++i) {
-        a.X[i] = xg;
-        a.Y[i] = zk(k0 + i);
-      }
-      te = tbeg();
-      HIPCHK(n2v2r_launch_spmm_tile(a, st));
-    } else {
-      SpmmArgs a{};
-      a.K = nk;
-      a.ldx = a.ldy = b;
-      // split over the XCDs like the split stage 2 (24.2 -> 23.4 us at cfg2); one GPU only,
-      // where every launch takes all layers
-      a.split = split2 ? 1 : 0;
-      for (int i = 0; i < nk; ++i) {
-        a.A[i] = h->layers[k0 + i]->csr_t();
-        a.X[i] = xg;
-        a.Y[i] = zk(k0 + i);
-      }
-      a.rpw = rpw1 = n2v2r_spmm_rpw(a, b);  // (the launcher's own choice, kept for n2v2r_gram_apply)
-      te = tbeg();
-      HIPCHK(n2v2r_launch_spmm(a, b, st));
-    }
-    tend(te, 0, bytes);
-  }
-
-  // Stage 1 of the gather forms.  Partitioned: every Z_k all-gathered for stage 2 -- one launch
-  // per layer, each Z_k gathered on the collective stream while the next layer's stage 1 runs, or
-  // (N2V2R_GATHER_OVERLAP=0, K = 1) one launch and the gathers in line.
-  void stage1_gathered(const float* xg) {
-    if (h->comm && K > 1 && gather_overlap() && st == h->stream) {
-      for (int k = 0; k < K; ++k) {
-        stage1(xg, k);
-        h->gather_panel_async(zk(k), gathered_z(k), b, k);
-      }
-      for (int k = 0; k < K; ++k) h->gather_wait(k);
-      return;
-    }
-    stage1(xg);
-    if (h->comm)
-      for (int k = 0; k < K; ++k) h->gather_panel(zk(k), gathered_z(k), b);
-  }
-
-  // Stage 2, flat: one launch summing the layers into W -- or (split2) leaving per-layer partials
-  // on the layers' XCDs, W pending until the next Gram pass or materialize() sums them.
-  void stage2_flat(float* Wout) {
-    SpmmArgs s{};
-    s.K = K;
-    s.sum = 1;
-    s.ldx = s.ldy = b;
-    for (int k = 0; k < K; ++k) {
-      s.A[k] = h->layers[k]->csr();
-      s.X[k] = stage2_in(k);
-    }
-    s.Y[0] = Wout;
-    if (split2) {
-      materialize();  // (a previous image is always consumed by now; kept for safety)
-      s.sum = 0;
-      s.split = 1;
-      for (int k = 0; k < K; ++k) s.Y[k] = s2part(k);
-      pending = Wout;
-    }
-    s.rpw = rpw2 = n2v2r_spmm_rpw(s, b);
-    const double bytes = stage_bytes(false);
-    const int te = tbeg();
-    HIPCHK(n2v2r_launch_spmm(s, b, st));
-    tend(te, 1, bytes);
-    for (int k = 0; k < K; ++k) {
-      const LayerDev& L = *h->layers[k];
-      algo_bytes += spmm_algo_bytes(L.nnz, L.unit, n, n, b) +
-                    spmm_algo_bytes(L.symmetric ? L.nnz : L.t_nnz,
-                                    L.symmetric ? L.unit : L.t_unit, n, n, b);
-    }
-    launches += 2;
-  }
-
-  // Stage 2, tiled column blocks: one launch over all layers
-  void stage2_tiled(float* Wout) {
-    SpmmTileArgs s{};
-    s.blk = h->ews.tblk.as<CsrBlk>() + (size_t)K * tile_nb;
-    s.ldx = s.ldy = 8;
-    s.n = n;
-    s.K = K;
-    s.nb = tile_nb;
-    s.sum = 1;
-    s.tile_rows = tile_rows;
-    s.wbits = tile_wb;
-    for (int k = 0; k < K; ++k) s.X[k] = stage2_in(k);
-    s.Y[0] = Wout;
-    const double b0 = stage_bytes(true), b1 = stage_bytes(false);
-    const int te = tbeg();
-    HIPCHK(n2v2r_launch_spmm_tile(s, st));
-    tend(te, 1, b1);
-    algo_bytes += b0 + b1;
-    launches += 2;
-  }
-
-  // Stage 2, reduce-scatter form (partitioned CSR handles, the default at W > 1, DESIGN section
-  // 6): after stage 1 on the all-gathered X, this rank's column share of stage 2,
-  // P = sum_k A_k[:, own rows] Z_k[own rows] over all (padded) global rows -- gathered from the
-  // rank's own Z rows only -- and ONE reduce-scatter of P into W's own rows: one all-gather + one
-  // reduce-scatter per application instead of K + 1 all-gathers.
-  void stage2_rs(float* Wout) {
-    const int64_t ng = (int64_t)h->world * npad;
-    float* P = h->ews.zg.as<float>();  // the gather form's Z panels' buffer (>= ng x b)
-    const double b0 = stage_bytes(true);
-    double b1 = 0.0;
-    SpmmArgs s2{};
-    s2.K = K;
-    s2.sum = 1;
-    s2.ldx = s2.ldy = b;
-    for (int k = 0; k < K; ++k) {
-      const LayerDev& L = *h->layers[k];
-      s2.A[k] = L.csr_c();
-      s2.X[k] = zk(k);
-      b1 += spmm_algo_bytes(L.c_nnz, s2.A[k].unit != 0, ng, npad, b);
-    }
-    s2.Y[0] = P;
-    // the whole share's choice, for every chunk: each row is summed as in one launch
-    s2.rpw = rpw2 = n2v2r_spmm_rpw(s2, b);
-    const int te = tbeg();
-    if (rs_chunks <= 1) {
-      HIPCHK(n2v2r_launch_spmm(s2, b, st));
-      tend(te, 1, b1);
-      h->comm->reduce_scatter_sum_f32(P, Wout, (size_t)npad * b, st);
-    } else {
-      // pipelined: the column share's rows are chunk-major (ensure_colcsr), so chunk c's product
-      // -- rows [c rs_rc, ...) of every rank's block -- is one contiguous range of P, reduce-
-      // scattered on the collective stream while chunk c + 1's product runs.  Every row is
-      // summed as in the one-launch form (same rows per wave), and every element of W sums the
-      // same ranks' values: the same result, with one chunk's reduce-scatter exposed.
-      const int W = h->world;
-      for (int c = 0; c < rs_chunks; ++c) {
-        const int64_t r0 = (int64_t)c * rs_rc;
-        const int64_t rows_c = std::min<int64_t>(rs_rc, npad - r0);
-        if (rows_c <= 0) break;
-        SpmmArgs sc = s2;
-        for (int k = 0; k < K; ++k) {
-          sc.A[k].indptr = s2.A[k].indptr + (size_t)r0 * W;
-          sc.A[k].n_rows = (int64_t)W * rows_c;
-        }
-        float* pc = P + (size_t)r0 * W * b;
-        sc.Y[0] = pc;
-        HIPCHK(n2v2r_launch_spmm(sc, b, st));
-        h->reduce_scatter_async(pc, Wout + (size_t)r0 * b, (size_t)rows_c * b);
-      }
-      tend(te, 1, b1);
-      h->rs_wait_all();
-    }
-    algo_bytes += b0 + b1;
-    launches += 2;
-  }
-
-  // Dense layers, both stages: Z_k = A_k^T X, W = sum_k A_k Z_k (fixed layer order), GEMMs on
-  // the local rows
-  void apply_M_dense(const float* xg, float* Wout) {
-    const int64_t ng = (int64_t)h->world * npad;  // rows of a gathered panel
-    // per GEMM launch: the layer rows read once (4 n N) + the panel read and the output rows
-    const double gb = 4.0 * (double)n * (double)h->n + 4.0 * (double)(ng + n) * b;
-    for (int k = 0; k < K; ++k) {
-      const LayerDev& L = *h->layers[k];
-      const int te = tbeg();
-      h->dense_apply(L.dense_at(), L.lda, xg, b, b, zk(k), b, 0.f, nullptr,
-                     h->comm ? nullptr : L.dense_a());
-      tend(te, 0, gb);
-    }
-    for (int k = 0; k < K; ++k) {
-      const LayerDev& L = *h->layers[k];
-      if (h->comm) h->gather_panel(zk(k), gathered_z(k), b);
-      const int te = tbeg();
-      h->dense_apply(L.dense_a(), L.lda, stage2_in(k), b, b, Wout, b, k == 0 ? 0.f : 1.f, nullptr,
-                     h->comm ? nullptr : L.dense_at());
-      tend(te, 1, gb);
-      algo_bytes += 2.0 * gb;
-    }
-    launches += 2 * K;
-  }
-
-  // W = M X = sum_k A_k (A_k^T X); X, W local, gathered panels for the column side
-  void apply_M(const float* X, float* Wout) {
-    const double t0 = now_ms();
-    lds_poison();
-    const float* xg = X;
-    if (h->comm) {
-      float* xgb = h->gath.as<float>();
-      h->gather_panel(X, xgb, b);
-      xg = xgb;
-    }
-    if (h->dense_layers()) {
-      apply_M_dense(xg, Wout);
-    } else if (rs_form) {
-      stage1(xg);
-      stage2_rs(Wout);
-    } else {
-      stage1_gathered(xg);
-      if (col_blocks)
-        stage2_tiled(Wout);
-      else
-        stage2_flat(Wout);
-    }
-    t_spmm += now_ms() - t0;
   }
 
   // ---- the orthogonalisation passes --------------------------------------------------------------
@@ -765,21 +434,21 @@ struct Eig {
     qz.push_back(const_cast<float*>(zin));
     const BlockList L = blocks(qz, 0, nq + 1);
     bool done = false;
-    if (pending && zin == pending && !p.cond && !h->comm) {
+    if (op.pending && zin == op.pending && !p.cond && !h->comm) {
       // the Gram pass that first reads the pending image also stores it
-      const float* parts[8];
-      for (int k = 0; k < K; ++k) parts[k] = s2part(k);
-      const hipError_t e = n2v2r_launch_ts_tn_zsum(L, n, parts, K, pending, part_p, part_n, gsm_p,
-                                                   st);
+      const float* parts[SPMM_MAX_LAYERS];
+      const int np = op.pending_parts(parts);
+      const hipError_t e = n2v2r_launch_ts_tn_zsum(L, n, parts, np, op.pending, part_p, part_n,
+                                                   gsm_p, st);
       if (e == hipSuccess) {
-        pending = nullptr;
+        op.stored();
         done = true;
       } else if (e != hipErrorNotSupported) {
         throw HipFail{e, "n2v2r_launch_ts_tn_zsum"};
       }
     }
     if (!done) {
-      if (zin == pending) materialize();
+      if (zin == op.pending) op.materialize();
       tn(L, one(zin), gsm_p, p.cond);
     }
     if (b == 8 && nq * b <= N2V2R_BAND_MAXC) {
@@ -812,7 +481,7 @@ struct Eig {
                       const std::vector<float*>* local = nullptr, double* save = nullptr,
                       bool lazy = false, double* rsave_first = nullptr) {
     const double t0 = now_ms();
-    lds_poison();
+    lds_poison(st);
     int* flg = flg_p;
     const std::vector<float*>& first = first_blocks(basis, local);
     // (no sticky flag here: a column the first pass cancelled -- scaled, not normalised -- is
@@ -875,7 +544,7 @@ struct Eig {
     if (h->ews.g2.bytes < sizeof(double) * 2 * (size_t)(nq_old + 2) * 64) return false;
     double* g2 = h->ews.g2.as<double>();
     const double t0 = now_ms();
-    lds_poison();
+    lds_poison(st);
     const BlockList L = blocks(all, 0, nq_old + 2);
     const hipError_t e = n2v2r_launch_ts_tn2(L, deferred, zb, n, part_p, part_n, g2, st);
     if (e == hipErrorNotSupported) return false;
@@ -922,7 +591,7 @@ struct Eig {
       // local pass; then either this block waits (its full pass with the next one) or the
       // waiting block and this one get their full passes
       const double t0 = now_ms();
-      lds_poison();
+      lds_poison(st);
       const std::vector<float*>& first = first_blocks(basis, &loc);
       // a refill or heavy cancellation here sets the sticky flag: the block may not go to its
       // SpMM before its full pass, so the cycle is expanded again without deferral
@@ -944,8 +613,8 @@ struct Eig {
     dbg(z, n * b, false, "orthonormalised Krylov block");
     dbg_ortho(z, basis, "Krylov block before its SpMM");
     float* w = take();
-    apply_M(z, w);
-    if (debug_finite()) materialize();
+    op.apply(z, w);
+    if (debug_finite()) op.materialize();
     dbg(w, n * b, false, "SpMM image M q");
     ++dbg_apps;
     qs.push_back(z);
@@ -963,80 +632,6 @@ struct Eig {
     }
     freelist.clear();
     for (auto& blk : h->ews.pool) freelist.push_back(blk->as<float>());
-    while ((int)h->ews.zk.size() < K) h->ews.zk.emplace_back(new DevBuf());
-    for (int k = 0; k < K; ++k) h->ews.zk[k]->ensure(bb);
-    if (h->comm) {
-      h->gath.ensure(sizeof(float) * h->world * npad * b);
-      h->ews.zg.ensure(sizeof(float) * (size_t)K * h->world * npad * b);
-    }
-  }
-
-  void setup_tiled_spmm() {
-    const int64_t nglob = h->n;
-    col_blocks = col_blocks_wanted(h, b);
-    if (!col_blocks) return;
-    // the flat-window tiled SpMM: column blocks (phases) per layer of <= 2 MB of panel, so a
-    // phase's block stays in the XCD's 4 MB L2 beside the index stream (cfg4: 16 blocks,
-    // 0.748 ms per stage launch; 8 blocks 0.896, 32 blocks 0.817: 4 MB blocks left 31 % of
-    // the gathers missing L2), at most 64 (cfg5's 320 MB panel, one layer launch: 4.36 ms at
-    // 64 blocks of 5 MB, 4.62 at 32 of 10 MB, 5.14 at 16 -- round 5, window offsets,
-    // profiles/r05_tile_cfg5.jsonl; with round 4's per-row block pointers 64 blocks lost).
-    // N2V2R_SPMM_TILE_NB = 4..64 overrides (read per fit).
-    int nb_auto = 4;
-    while (nb_auto < 64 && (double)nglob * 32.0 / nb_auto > 2.0 * 1024 * 1024) nb_auto *= 2;
-    const char* tn_ = std::getenv("N2V2R_SPMM_TILE_NB");
-    tile_nb = tn_ ? std::atoi(tn_) : nb_auto;
-    if (tile_nb != 4 && tile_nb != 8 && tile_nb != 16 && tile_nb != 32 && tile_nb != 64 &&
-        tile_nb != 128)
-      tile_nb = nb_auto;
-    // packed entries need the in-block column bits to fit beside the row-in-window bits
-    // (always, for N < 2^26 per block); otherwise the row kernel runs
-    tile_wb = tile_wbits(h->layers, tile_nb);
-    for (auto& Lp : h->layers)
-      col_blocks = ensure_col_blocks(*Lp, nglob, st, tile_nb, tile_wb) && col_blocks;
-    if (!col_blocks) return;
-    int ncu = 0;
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
-    tile_rows = n2v2r_spmm_tile_rows(n, ncu, 2, tile_wb);
-    const int nb = tile_nb;
-    std::vector<CsrBlk> hb((size_t)2 * K * nb);
-    for (int k = 0; k < K; ++k) {
-      const LayerDev& L = *h->layers[k];
-      for (int j = 0; j < nb; ++j) {
-        hb[(size_t)k * nb + j] = (L.symmetric ? L.cb : L.cb_t).blk[j];
-        hb[(size_t)(K + k) * nb + j] = L.cb.blk[j];
-      }
-    }
-    h->ews.tblk.ensure(sizeof(CsrBlk) * hb.size());
-    HIPCHK(hipMemcpyAsync(h->ews.tblk.p, hb.data(), sizeof(CsrBlk) * hb.size(),
-                          hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));  // hb dies here
-  }
-
-  // the second SpMM stage's form: a reduce-scatter on a row partition, XCD-split on one GPU
-  void setup_stage2_form() {
-    rs_form = false;
-    if (h->comm && !h->dense_layers()) {
-      // read per fit (tests, A/B runs): "rs" / "gather" force a form; unset: the reduce-scatter
-      // when there is more than one rank (one rank's "column share" is every row: its stage 2
-      // would gather from the whole Z with the row kernel, slower than the tiled gather form)
-      const char* e = std::getenv("N2V2R_DIST_STAGE2");
-      rs_form = e && std::strcmp(e, "rs") == 0 ? true
-                : e && std::strcmp(e, "gather") == 0 ? false
-                : h->world > 1;
-      if (rs_form) {
-        const char* ce = std::getenv("N2V2R_RS_CHUNKS");  // read per fit (tests, A/B runs)
-        rs_chunks = std::max(1, std::min(SPMM_MAX_LAYERS, ce ? std::atoi(ce) : 4));
-        rs_rc = (npad + rs_chunks - 1) / rs_chunks;
-        rs_chunks = (int)((npad + rs_rc - 1) / rs_rc);
-        if (rs_chunks <= 1) rs_rc = 0;
-        for (auto& Lp : h->layers)
-          ensure_colcsr(*Lp, h->n, (int64_t)h->world * npad, st, npad, h->world, rs_rc);
-      }
-    }
-    split2 = split2_wanted(h, b) && !col_blocks;
-    pending = nullptr;
-    if (split2) h->ews.s2part.ensure(sizeof(float) * (size_t)K * npad * 8);
   }
 
   // every scratch buffer's size, and with them which Rayleigh-Ritz forms and images the fit has
@@ -1097,6 +692,18 @@ struct Eig {
     h->ews.tflag.ensure(sizeof(double) * 2);
     wh.assign(keep, 0.0);
     res2.assign(keep, 0.0);
+  }
+
+  // A plan without a fit (the diagnostic entries): block width, kept vectors and basis blocks as
+  // given, the pool and the scratch as run() sets them up for that plan
+  void set_plan(int b_, int keep_, int nblk) {
+    b = b_;
+    keep = keep_;
+    pb = keep / b;
+    nb_max = nblk;
+    c_max = nblk * b;
+    reuse_pool();
+    size_scratch();
   }
 
   // the reorthogonalisation threshold and the deferral of full passes (needs `lean`)
@@ -1163,16 +770,16 @@ struct Eig {
   double launch_rr(RrForm form, int nq) {
     const int c = nq * b;
     double* trid = h->ews.tri.as<double>();
-    materialize();  // W.back() (every other W block was stored by its expansion's Gram pass)
+    op.materialize();  // W.back() (every other W block was stored by its expansion's Gram pass)
     const double tr0 = now_ms();
-    lds_poison();
+    lds_poison(st);
     if (banded(form)) {
       const std::vector<float*> loc = local_of(Q);
       tn(blocks(loc, 0, (int)loc.size()), one(W.back()),
          h->ews.hband.as<double>() + band_off(nq - 1), nullptr);
       if (!rr_armed) HIPCHK(hipMemsetAsync(h->ews.rrerr.as<int>(), 0, 4 * sizeof(int), st));
       rr_armed = true;  // from here on each read-back zeroes the words it reads
-      lds_poison();
+      lds_poison(st);
       if (form == RrForm::Sturm) {
         HIPCHK(n2v2r_launch_rr_sturm(h->ews.hband.as<double>(), c, kry0 * b,
                                      h->theta.as<double>(), h->ews.sturm.as<double>(),
@@ -1198,7 +805,7 @@ struct Eig {
         tn(blocks(Q, 0, nq), blocks(W, 0, nq), h->ews.gsmall.as<double>(), nullptr);
       }
       dbg(h->ews.gsmall.p, (int64_t)c * c, true, "projected matrix H = Q^T W");
-      lds_poison();
+      lds_poison(st);
       // ranks that share this device (thread group): their concurrent launches of the
       // multi-workgroup form could not all be resident, so they keep the one-workgroup kernel;
       // so does a fit whose multi-workgroup launch once timed out (tri_err, rr_next)
@@ -1210,12 +817,12 @@ struct Eig {
                                      coop ? h->ews.trcoop.p : nullptr, st));
       dbg(trid, c, true, "tridiagonal diagonal");
       dbg(trid + c_max, c - 1, true, "tridiagonal off-diagonal");
-      lds_poison();
+      lds_poison(st);
       HIPCHK(n2v2r_launch_rr_tri_eig(trid, trid + c_max, c, keep, h->theta.as<double>(),
                                      h->ews.ytri.as<double>(), h->ews.tscr.as<double>(), st));
       dbg(h->theta.p, keep, true, "tridiagonal eigenvalues (bisection)");
       dbg(h->ews.ytri.p, (int64_t)c * keep, true, "tridiagonal eigenvectors");
-      lds_poison();
+      lds_poison(st);
       HIPCHK(n2v2r_launch_rr_backtransform(h->ews.refl.as<double>(), trid + 2 * c_max, c,
                                            h->ews.ytri.as<double>(), keep,
                                            h->ews.csmall.as<float>(), keep,
@@ -1229,7 +836,7 @@ struct Eig {
 
   // Ritz vectors X = Q S, MX = W S (keep columns, pb blocks; lean images: X only)
   void ritz_vectors(int nq) {
-    lds_poison();
+    lds_poison(st);
     const int per_launch = std::max(1, 128 / b);  // output blocks per ts_nn launch (<= 128 cols)
     ritz_done = false;
     ritz_launches = 0;
@@ -1457,17 +1064,17 @@ struct Eig {
     // one GPU, tiled SpMM, every column of the embedding covered: keep the stage-1 products
     // (N2V2R_YCAP=0, read per fit: the embedding step computes its SpMM launches; A/B, tests)
     const char* ycv = std::getenv("N2V2R_YCAP");
-    const bool cap = col_blocks && !h->comm && b == 8 && qd * b == ldu &&
+    const bool cap = op.col_blocks && !h->comm && b == 8 && qd * b == ldu &&
                      !(ycv && ycv[0] == '0');
     if (cap) h->Y.ensure(sizeof(float) * (size_t)K * npad * ldu, st);
     for (int q = 0; q < qd; ++q) {
       MV[q] = take();
-      apply_M(X[q], MV[q]);
-      materialize();
+      op.apply(X[q], MV[q]);
+      op.materialize();
       if (cap)
         for (int k = 0; k < K; ++k)
           HIPCHK(hipMemcpy2DAsync(h->Y.as<float>() + (size_t)k * npad * ldu + (size_t)q * b,
-                                  sizeof(float) * ldu, h->ews.zk[k]->as<float>(),
+                                  sizeof(float) * ldu, op.zk(k),
                                   sizeof(float) * b, sizeof(float) * b, n,
                                   hipMemcpyDeviceToDevice, st));
     }
@@ -1527,7 +1134,7 @@ struct Eig {
     if (lean) {
       E.push_back(E_lean);
       EW.push_back(take());
-      apply_M(E_lean, EW[0]);
+      op.apply(E_lean, EW[0]);
     } else {
       expand_one(W.back(), Q, E, EW);
     }
@@ -1541,9 +1148,6 @@ struct Eig {
     kry0 = pb;
   }
 
-  // the application's form as n2v2r_eig_stats.spmm_form codes it
-  int spmm_form() const { return h->dense_layers() ? 4 : col_blocks ? 5 : split2 ? 1 : 0; }
-
   void fill_stats() {
     if (!stats) return;
     stats->restarts = cycle + 1;
@@ -1552,21 +1156,21 @@ struct Eig {
     stats->basis = c_max;
     stats->max_residual = maxres;
     stats->ms_total = now_ms() - t_start;
-    stats->ms_spmm = t_spmm;
+    stats->ms_spmm = op.t_spmm;
     stats->ms_ortho = t_ortho;
     stats->ms_rr_host = t_rr;
-    stats->spmm_launches = launches;
-    stats->spmm_algo_bytes = algo_bytes;
+    stats->spmm_launches = op.launches;
+    stats->spmm_algo_bytes = op.algo_bytes;
     stats->stagnated = stagnated;
     stats->rr_fallbacks = stats_rr_fallbacks;
     stats->est_scale = est_scale;
     stats->lean_checks = lean_checks;
     stats->pool_blocks = (int)h->ews.pool.size();
-    stats->spmm_form = spmm_form();
+    stats->spmm_form = op.spmm_form();
     stats->stag_cap = stag_cap;
     stats->y_captured = y_captured ? 1 : 0;
     stats->tri_fallbacks = tri_fallbacks;
-    tsum(stats);
+    op.tsum(stats);
   }
 
   int run(int d_, const n2v2r_eig_opts& o, std::vector<double>& theta_out, float* Uout,
@@ -1575,10 +1179,7 @@ struct Eig {
     seed = o.seed ? o.seed : 0x5EEDull;
     flags = o.solver_flags;
     full_first = flag(N2V2R_EIG_FULL_FIRST_PASS);
-    time_spmm = flag(N2V2R_EIG_TIME_SPMM);
     tri_test_armed = flag(N2V2R_EIG_TEST_TRI_TIMEOUT);
-    tkind.clear();
-    tbytes.clear();
     kry0 = 0;
     tol = o.tol > 0 ? o.tol : 1e-6;
     max_restarts = o.max_restarts > 0 ? o.max_restarts : 2000;
@@ -1598,8 +1199,7 @@ struct Eig {
     // N2V2R_ERR_NO_CONVERGENCE.
     stag_cap = 2.0 * std::max(tol, std::sqrt((double)c_max) * 0x1p-24);
     reuse_pool();
-    setup_tiled_spmm();
-    setup_stage2_form();
+    op.setup(b, flag(N2V2R_EIG_TIME_SPMM));
     size_scratch();
     read_reorth_switches();
     poison_scratch();
@@ -1611,8 +1211,8 @@ struct Eig {
     orthonormalize(q0, {});
     dbg(q0, n * b, false, "orthonormalised start block");
     W.assign(1, take());
-    apply_M(Q[0], W[0]);
-    if (debug_finite()) materialize();
+    op.apply(Q[0], W[0]);
+    if (debug_finite()) op.materialize();
     dbg(W[0], n * b, false, "SpMM image of the start block");
     if (flag(N2V2R_EIG_TEST_FAIL_ALONE) && h->comm && h->rank == 1)
       throw StatusFail{N2V2R_ERR_INTERNAL, "test: rank 1 fails alone"};
@@ -1708,7 +1308,7 @@ struct Eig {
       }
       restart();
     }
-    materialize();
+    op.materialize();
     if (trace() && reorth_tol != 0.f) {
       int sk[65] = {};
       HIPCHK(hipMemcpyAsync(sk, h->ews.skipc.p, sizeof(int) * 65, hipMemcpyDeviceToHost, st));
@@ -1731,22 +1331,6 @@ struct Eig {
   }
 };
 
-bool col_blocks_wanted(const n2v2r_handle* h, int b) {
-  if (b != 8 || h->dense_layers() || h->layers.empty()) return false;
-  const char* e = std::getenv("N2V2R_SPMM_CB");
-  if (e && e[0] == '1') return true;
-  if (e && e[0] == '0') return false;
-  // measured (tools/cb_probe.py, one layer, HIP events): row kernel / column blocks =
-  // 0.56 at a 3.2 MB panel (N = 100k: the panel already fits one L2), 1.35 at 9.6 MB,
-  // 1.61 at 32 MB, 1.16 at 96 MB, 0.93 at 320 MB (beyond the Infinity Cache the gathers go
-  // to HBM either way and the partials only add traffic)
-  // round 3: the flat-window tiled form also wins beyond the Infinity Cache -- each phase
-  // gathers from one panel block, which the Infinity Cache holds even when the whole panel does
-  // not (cfg5 on one GPU, 320 MB panel: 9.5 vs 11.5 ms per stage launch) -- so the window has no
-  // upper end
-  const double panel = 4.0 * b * (double)h->n;
-  return panel > 8.0e6;
-}
 // layer k's local rows (nloc x d, the embedding's first d of its ldy columns) to Y + k * stride
 void copy_embedding(n2v2r_handle* h, float* Y, int64_t layer_stride) {
   HIPCHK(hipSetDevice(h->device));
@@ -1757,6 +1341,106 @@ void copy_embedding(n2v2r_handle* h, float* Y, int64_t layer_stride) {
                             hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
 }
+
+// The embedding of a finished fit from its left vectors U (h->U, ld ldu) and Ritz values theta:
+// deterministic signs, sigma = sqrt(theta), and Y_k = A_k^T U sigma^(-1/2) into h->Y -- the
+// products the final lean check captured (`captured`), the fit's tiled SpMM, or the row kernel /
+// the dense GEMM.
+static void build_embedding(n2v2r_handle* h, const GramOp& op, const std::vector<double>& theta,
+                            int ldu, bool captured) {
+  const int d = (int)theta.size(), b = op.b;
+  const bool tiled = op.col_blocks;  // (b = 8 then)
+  // deterministic signs: largest-magnitude entry of every column of U positive
+  h->keys.ensure(sizeof(unsigned long long) * 1024 * (size_t)ldu);
+  h->best.ensure(sizeof(unsigned long long) * ldu);
+  h->colscale.ensure(sizeof(float) * ldu);
+  HIPCHK(n2v2r_launch_colmax_keys(h->U.as<float>(), ldu, h->nloc, d, h->row0,
+                                  h->keys.as<unsigned long long>(), 1024 * (size_t)ldu,
+                                  h->best.as<unsigned long long>(), h->stream));
+  if (h->comm)
+    h->comm->allreduce_max_u64(h->best.as<unsigned long long>(), ldu, h->stream);
+  HIPCHK(n2v2r_launch_colmax_sign(h->best.as<unsigned long long>(), ldu, h->U.as<float>(), ldu, d,
+                                  h->row0, h->nloc, h->colscale.as<float>(), h->stream));
+  if (h->comm)
+    h->comm->allreduce_sum_f32(h->colscale.as<float>(), ldu, h->stream);
+  HIPCHK(n2v2r_launch_scale_cols(h->U.as<float>(), ldu, h->npad, h->colscale.as<float>(),
+                                 h->stream));
+  // Y_k = A_k^T U diag(theta)^(-1/4)  (sigma = sqrt(theta); V sqrt(sigma) = A^T U sigma^-1/2)
+  h->d = d;
+  h->ldy = ldu;
+  h->sigma.assign(d, 0.0);
+  std::vector<float> sc(ldu, 0.f);
+  for (int j = 0; j < d; ++j) {
+    h->sigma[j] = std::sqrt(std::max(theta[j], 0.0));
+    sc[j] = h->sigma[j] > 0 ? (float)(1.0 / std::sqrt(h->sigma[j])) : 0.f;
+  }
+  if (captured) {
+    // the captured A_k^T X come from the Ritz vectors before the sign pass: fold each column's
+    // sign (+-1, exact) into its scale
+    std::vector<float> sgn(ldu, 1.f);
+    HIPCHK(hipMemcpyAsync(sgn.data(), h->colscale.p, sizeof(float) * ldu, hipMemcpyDeviceToHost,
+                          h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int j = 0; j < d; ++j) sc[j] *= sgn[j];
+  }
+  HIPCHK(hipMemcpyAsync(h->colscale.p, sc.data(), sizeof(float) * ldu, hipMemcpyHostToDevice,
+                        h->stream));
+  const float* ug = h->U.as<float>();
+  DevBuf ugath;
+  if (h->comm) {
+    ugath.ensure(sizeof(float) * h->world * h->npad * ldu);
+    h->gather_panel(h->U.as<float>(), ugath.as<float>(), ldu);
+    ug = ugath.as<float>();
+  }
+  h->Y.ensure(sizeof(float) * (size_t)h->K * h->npad * ldu);
+  if (h->dense_layers()) {
+    for (int k = 0; k < h->K; ++k) {
+      const LayerDev& L = *h->layers[k];
+      // one GEMM per layer over all ldu columns (ldu <= 256: 64-column slices)
+      for (int q = 0; q * 64 < ldu; ++q)
+        h->dense_apply(L.dense_at(), L.lda, ug + q * 64, ldu, std::min(64, ldu - q * 64),
+                       h->Y.as<float>() + (size_t)k * h->npad * ldu + q * 64, ldu, 0.f,
+                       h->colscale.as<float>() + q * 64);
+    }
+  }
+  if (!h->dense_layers() && tiled) {
+    // the fit's tiled SpMM (stage-1 blocks, A_k^T) on b-column slices of U copied to a
+    // contiguous panel, then one column scaling of every Y_k (the row kernel below gathers
+    // 32 B out of each 512-B row of U -- a 512 MB panel at cfg4 -- and scales in-kernel)
+    const int64_t ng = h->comm ? (int64_t)h->world * h->npad : h->npad;
+    DevBuf& panel = h->ypanel;
+    panel.ensure_raw(sizeof(float) * ng * 8);
+    SpmmTileArgs a = op.tile_args(false, 0, h->K, 0, ldu);
+    for (int q = 0; !captured && q * 8 < ldu; ++q) {
+      HIPCHK(hipMemcpy2DAsync(panel.p, sizeof(float) * 8, ug + q * 8, sizeof(float) * ldu,
+                              sizeof(float) * 8, ng, hipMemcpyDeviceToDevice, h->stream));
+      for (int k = 0; k < h->K; ++k) {
+        a.X[k] = panel.as<float>();
+        a.Y[k] = h->Y.as<float>() + (size_t)k * h->npad * ldu + q * 8;
+      }
+      HIPCHK(n2v2r_launch_spmm_tile(a, h->stream));
+    }
+    for (int k = 0; k < h->K; ++k)
+      HIPCHK(n2v2r_launch_scale_cols(h->Y.as<float>() + (size_t)k * h->npad * ldu, ldu,
+                                     h->npad, h->colscale.as<float>(), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // the panel dies here
+  }
+  for (int q = 0; !h->dense_layers() && !tiled && q * b < ldu; ++q) {
+    SpmmArgs a{};
+    a.K = h->K;
+    a.sum = 0;
+    a.ldx = ldu;
+    a.ldy = ldu;
+    a.colscale = h->colscale.as<float>() + q * b;
+    for (int k = 0; k < h->K; ++k) {
+      a.A[k] = h->layers[k]->csr_t();
+      a.X[k] = ug + q * b;
+      a.Y[k] = h->Y.as<float>() + (size_t)k * h->npad * ldu + q * b;
+    }
+    HIPCHK(n2v2r_launch_spmm(a, b, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+}
 }  // namespace n2v2r_int
 
 extern "C" {
@@ -1764,15 +1448,7 @@ extern "C" {
 int n2v2r_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_stats* stats) {
   if (h && h->multi()) return multi_uase(h, d, opts, stats);
   return guarded(h, [&]() -> int {
-    if (h->K < 1) {
-      h->err = "no layers set";
-      return N2V2R_ERR_BAD_ARG;
-    }
-    for (auto& L : h->layers)
-      if (!L->loaded) {
-        h->err = "a layer was not loaded";
-        return N2V2R_ERR_BAD_ARG;
-      }
+    if (!layers_ready(h)) return N2V2R_ERR_BAD_ARG;
     // d <= 600: the kept Ritz vectors (max(d + 16, 5 d / 4)) plus one block must fit the
     // Rayleigh-Ritz kernels' 768-column basis
     if (d < 1 || d > 600 || d >= h->n) {
@@ -1796,135 +1472,23 @@ int n2v2r_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_sta
     h->U.ensure(sizeof(float) * h->npad * ldu);
     HIPCHK(hipMemsetAsync(h->U.p, 0, sizeof(float) * h->npad * ldu, h->stream));
     std::vector<double> theta;
-    int st = 0, b = 0;
-    // the fit's tiled column-block configuration, reused for the embedding images below
-    bool ytile = false, ycap = false;
-    int ytile_rows = 0, ytile_nb = 0, ytile_wb = 0;
+    int st = 0;
+    std::optional<Eig> eig;
     for (int attempt = 0;; ++attempt) {
-      Eig eig{};
-      eig.h = h;
-      eig.st = h->stream;
-      eig.n = h->nloc;
-      eig.npad = h->npad;
-      eig.row0 = h->row0;
-      eig.K = h->K;
-      eig.stats = stats;
-      eig.lean_off = attempt > 0;
+      eig.emplace(h);
+      eig->stats = stats;
+      eig->lean_off = attempt > 0;
       try {
-        st = eig.run(d, o, theta, h->U.as<float>(), ldu);
+        st = eig->run(d, o, theta, h->U.as<float>(), ldu);
       } catch (const Eig::LeanRetry&) {
         // lean images cannot take the dense Rayleigh-Ritz fallback: the fit again with images
         fprintf(stderr, "[n2v2r] banded Rayleigh-Ritz failed under lean images; fit rerun\n");
         HIPCHK(hipStreamSynchronize(h->stream));
         continue;
       }
-      b = eig.b;
-      ytile = eig.col_blocks && eig.b == 8;
-      ycap = ytile && eig.y_captured;
-      ytile_rows = eig.tile_rows;
-      ytile_wb = eig.tile_wb;
-      ytile_nb = eig.tile_nb;
       break;
     }
-    // deterministic signs: largest-magnitude entry of every column of U positive
-    h->keys.ensure(sizeof(unsigned long long) * 1024 * (size_t)ldu);
-    h->best.ensure(sizeof(unsigned long long) * ldu);
-    h->colscale.ensure(sizeof(float) * ldu);
-    HIPCHK(n2v2r_launch_colmax_keys(h->U.as<float>(), ldu, h->nloc, d, h->row0,
-                                    h->keys.as<unsigned long long>(), 1024 * (size_t)ldu,
-                                    h->best.as<unsigned long long>(), h->stream));
-    if (h->comm)
-      h->comm->allreduce_max_u64(h->best.as<unsigned long long>(), ldu, h->stream);
-    HIPCHK(n2v2r_launch_colmax_sign(h->best.as<unsigned long long>(), ldu, h->U.as<float>(), ldu, d,
-                                    h->row0, h->nloc, h->colscale.as<float>(), h->stream));
-    if (h->comm)
-      h->comm->allreduce_sum_f32(h->colscale.as<float>(), ldu, h->stream);
-    HIPCHK(n2v2r_launch_scale_cols(h->U.as<float>(), ldu, h->npad, h->colscale.as<float>(),
-                                   h->stream));
-    // Y_k = A_k^T U diag(theta)^(-1/4)  (sigma = sqrt(theta); V sqrt(sigma) = A^T U sigma^-1/2)
-    h->d = d;
-    h->ldy = ldu;
-    h->sigma.assign(d, 0.0);
-    std::vector<float> sc(ldu, 0.f);
-    for (int j = 0; j < d; ++j) {
-      h->sigma[j] = std::sqrt(std::max(theta[j], 0.0));
-      sc[j] = h->sigma[j] > 0 ? (float)(1.0 / std::sqrt(h->sigma[j])) : 0.f;
-    }
-    if (ycap) {
-      // the captured A_k^T X come from the Ritz vectors before the sign pass: fold each column's
-      // sign (+-1, exact) into its scale
-      std::vector<float> sgn(ldu, 1.f);
-      HIPCHK(hipMemcpyAsync(sgn.data(), h->colscale.p, sizeof(float) * ldu, hipMemcpyDeviceToHost,
-                            h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-      for (int j = 0; j < d; ++j) sc[j] *= sgn[j];
-    }
-    HIPCHK(hipMemcpyAsync(h->colscale.p, sc.data(), sizeof(float) * ldu, hipMemcpyHostToDevice,
-                          h->stream));
-    const float* ug = h->U.as<float>();
-    DevBuf ugath;
-    if (h->comm) {
-      ugath.ensure(sizeof(float) * h->world * h->npad * ldu);
-      h->gather_panel(h->U.as<float>(), ugath.as<float>(), ldu);
-      ug = ugath.as<float>();
-    }
-    h->Y.ensure(sizeof(float) * (size_t)h->K * h->npad * ldu);
-    if (h->dense_layers()) {
-      for (int k = 0; k < h->K; ++k) {
-        const LayerDev& L = *h->layers[k];
-        // one GEMM per layer over all ldu columns (ldu <= 256: 64-column slices)
-        for (int q = 0; q * 64 < ldu; ++q)
-          h->dense_apply(L.dense_at(), L.lda, ug + q * 64, ldu, std::min(64, ldu - q * 64),
-                         h->Y.as<float>() + (size_t)k * h->npad * ldu + q * 64, ldu, 0.f,
-                         h->colscale.as<float>() + q * 64);
-      }
-    }
-    if (!h->dense_layers() && ytile) {
-      // the fit's tiled SpMM (stage-1 blocks, A_k^T) on b-column slices of U copied to a
-      // contiguous panel, then one column scaling of every Y_k (the row kernel below gathers
-      // 32 B out of each 512-B row of U -- a 512 MB panel at cfg4 -- and scales in-kernel)
-      const int64_t ng = h->comm ? (int64_t)h->world * h->npad : h->npad;
-      DevBuf& panel = h->ypanel;
-      panel.ensure_raw(sizeof(float) * ng * 8);
-      SpmmTileArgs a{};
-      a.blk = h->ews.tblk.as<CsrBlk>();
-      a.ldx = 8;
-      a.ldy = ldu;
-      a.n = h->nloc;
-      a.K = h->K;
-      a.nb = ytile_nb;
-      a.sum = 0;
-      a.tile_rows = ytile_rows;
-      a.wbits = ytile_wb;
-      for (int q = 0; !ycap && q * 8 < ldu; ++q) {
-        HIPCHK(hipMemcpy2DAsync(panel.p, sizeof(float) * 8, ug + q * 8, sizeof(float) * ldu,
-                                sizeof(float) * 8, ng, hipMemcpyDeviceToDevice, h->stream));
-        for (int k = 0; k < h->K; ++k) {
-          a.X[k] = panel.as<float>();
-          a.Y[k] = h->Y.as<float>() + (size_t)k * h->npad * ldu + q * 8;
-        }
-        HIPCHK(n2v2r_launch_spmm_tile(a, h->stream));
-      }
-      for (int k = 0; k < h->K; ++k)
-        HIPCHK(n2v2r_launch_scale_cols(h->Y.as<float>() + (size_t)k * h->npad * ldu, ldu,
-                                       h->npad, h->colscale.as<float>(), h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));  // the panel dies here
-    }
-    for (int q = 0; !h->dense_layers() && !ytile && q * b < ldu; ++q) {
-      SpmmArgs a{};
-      a.K = h->K;
-      a.sum = 0;
-      a.ldx = ldu;
-      a.ldy = ldu;
-      a.colscale = h->colscale.as<float>() + q * b;
-      for (int k = 0; k < h->K; ++k) {
-        a.A[k] = h->layers[k]->csr_t();
-        a.X[k] = ug + q * b;
-        a.Y[k] = h->Y.as<float>() + (size_t)k * h->npad * ldu + q * b;
-      }
-      HIPCHK(n2v2r_launch_spmm(a, b, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    build_embedding(h, eig->op, theta, ldu, eig->y_captured);
     h->have_embedding = true;
     h->ncmp = h->ncols = 0;
     if (st != N2V2R_OK)
@@ -1932,72 +1496,6 @@ int n2v2r_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_sta
                  stats ? stats->max_residual : -1.0, o.tol > 0 ? o.tol : 1e-6,
                  stats && stats->stagnated ? "; stopped flat above the fp32-floor cap" : "");
     return st;
-  });
-}
-
-// One application of M alone (tests): an Eig set up as a fit's, its apply_M on a host panel.
-int n2v2r_gram_apply(n2v2r_handle* h, int b, const float* X, float* Z, float* W,
-                     n2v2r_gram_info* info) {
-  return guarded(h, [&]() -> int {
-    if (h->multi() || (b != 8 && b != 16 && b != 32 && b != 64) || !X || !W) return N2V2R_ERR_BAD_ARG;
-    if (h->K < 1) {
-      h->err = "no layers set";
-      return N2V2R_ERR_BAD_ARG;
-    }
-    for (auto& L : h->layers)
-      if (!L->loaded) {
-        h->err = "a layer was not loaded";
-        return N2V2R_ERR_BAD_ARG;
-      }
-    Eig eig{};
-    eig.h = h;
-    eig.st = h->stream;
-    eig.n = h->nloc;
-    eig.npad = h->npad;
-    eig.row0 = h->row0;
-    eig.K = h->K;
-    eig.b = b;
-    eig.stats = nullptr;
-    eig.reuse_pool();
-    eig.setup_tiled_spmm();
-    eig.setup_stage2_form();
-    hipStream_t st = eig.st;
-    float* x = eig.take();
-    float* w = eig.take();
-    // NaN bytes wherever the application has to write: the local rows of W, of every Z_k and of
-    // the split form's partials (padding rows stay the zeros the solver keeps there), and a rank's
-    // gathered panels whole (the collectives write all of them, or all that is read)
-    const size_t rows = sizeof(float) * (size_t)eig.n * b;
-    HIPCHK(hipMemsetAsync(w, 0xFF, rows, st));
-    for (int k = 0; k < eig.K; ++k) HIPCHK(hipMemsetAsync(eig.zk(k), 0xFF, rows, st));
-    if (eig.split2)
-      for (int k = 0; k < eig.K; ++k) HIPCHK(hipMemsetAsync(eig.s2part(k), 0xFF, rows, st));
-    if (h->comm) {
-      HIPCHK(hipMemsetAsync(h->gath.p, 0xFF, h->gath.bytes, st));
-      HIPCHK(hipMemsetAsync(h->ews.zg.p, 0xFF, h->ews.zg.bytes, st));
-    }
-    HIPCHK(hipMemcpyAsync(x, X + (size_t)eig.row0 * b, rows, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));  // pageable source: complete before the kernels
-    eig.apply_M(x, w);
-    eig.materialize();
-    HIPCHK(hipMemcpyAsync(W, w, rows, hipMemcpyDeviceToHost, st));
-    if (Z)
-      for (int k = 0; k < eig.K; ++k)
-        HIPCHK(hipMemcpyAsync(Z + (size_t)k * eig.n * b, eig.zk(k), rows, hipMemcpyDeviceToHost,
-                              st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (info) {
-      info->form = eig.spmm_form();
-      info->rs_form = eig.rs_form ? 1 : 0;
-      info->rs_chunks = eig.rs_form ? eig.rs_chunks : 0;
-      info->split2 = eig.split2 ? 1 : 0;
-      info->tile_nb = eig.col_blocks ? eig.tile_nb : 0;
-      info->tile_wb = eig.col_blocks ? eig.tile_wb : 0;
-      info->tile_rows = eig.col_blocks ? eig.tile_rows : 0;
-      info->rpw1 = eig.rpw1;
-      info->rpw2 = eig.rpw2;
-    }
-    return N2V2R_OK;
   });
 }
 
@@ -2011,31 +1509,10 @@ int n2v2r_ritz_step(n2v2r_handle* h, int b, int nq, int keep, int lean, const fl
         keep % b != 0 || (int64_t)keep + b > (int64_t)nq * b || (int64_t)nq * b > N2V2R_BAND_MAXC ||
         (lean && b != 8) || !Q || !S || !theta || !X || (!lean && (!W || !MX || !res)))
       return N2V2R_ERR_BAD_ARG;
-    if (h->K < 1) {
-      h->err = "no layers set";
-      return N2V2R_ERR_BAD_ARG;
-    }
-    for (auto& L : h->layers)
-      if (!L->loaded) {
-        h->err = "a layer was not loaded";
-        return N2V2R_ERR_BAD_ARG;
-      }
-    Eig eig{};
-    eig.h = h;
-    eig.st = h->stream;
-    eig.n = h->nloc;
-    eig.npad = h->npad;
-    eig.row0 = h->row0;
-    eig.K = h->K;
-    eig.b = b;
-    eig.keep = keep;
-    eig.pb = keep / b;
-    eig.nb_max = nq;
-    eig.c_max = nq * b;
-    eig.stats = nullptr;
-    eig.reuse_pool();
-    eig.size_scratch();
-    eig.lean = lean != 0;  // (size_scratch chose what a fit of this plan would take)
+    if (!layers_ready(h)) return N2V2R_ERR_BAD_ARG;
+    Eig eig(h);
+    eig.set_plan(b, keep, nq);
+    eig.lean = lean != 0;  // (set_plan chose what a fit of this plan would take)
     hipStream_t st = eig.st;
     const int pb = eig.pb;
     const size_t rows = sizeof(float) * (size_t)eig.n * b;
@@ -2084,29 +1561,8 @@ static int diag_eig(n2v2r_handle* h, int b, int nblk, Eig& eig) {
   if (h->multi() || h->comm || (b != 8 && b != 16 && b != 32 && b != 64) || nblk < 1 ||
       (int64_t)nblk * b > N2V2R_BAND_MAXC)
     return N2V2R_ERR_BAD_ARG;
-  if (h->K < 1) {
-    h->err = "no layers set";
-    return N2V2R_ERR_BAD_ARG;
-  }
-  for (auto& L : h->layers)
-    if (!L->loaded) {
-      h->err = "a layer was not loaded";
-      return N2V2R_ERR_BAD_ARG;
-    }
-  eig.h = h;
-  eig.st = h->stream;
-  eig.n = h->nloc;
-  eig.npad = h->npad;
-  eig.row0 = h->row0;
-  eig.K = h->K;
-  eig.b = b;
-  eig.keep = b;
-  eig.pb = 1;
-  eig.nb_max = nblk;
-  eig.c_max = nblk * b;
-  eig.stats = nullptr;
-  eig.reuse_pool();
-  eig.size_scratch();
+  if (!layers_ready(h)) return N2V2R_ERR_BAD_ARG;
+  eig.set_plan(b, b, nblk);
   return N2V2R_OK;
 }
 
@@ -2130,7 +1586,7 @@ int n2v2r_block_gram(n2v2r_handle* h, int b, int na, int nb, const float* A, con
                      double* G, n2v2r_pass_info* info) {
   return guarded(h, [&]() -> int {
     if (na < 1 || nb < 1 || !A || !B || !G) return N2V2R_ERR_BAD_ARG;
-    Eig eig{};
+    Eig eig(h);
     if (const int s = diag_eig(h, b, std::max(na, nb), eig)) return s;
     if (const int s = diag_gram_info(eig, na, nb, info)) return s;
     hipStream_t st = eig.st;
@@ -2165,7 +1621,7 @@ int n2v2r_ortho_pass(n2v2r_handle* h, int b, int nq, const float* Q, float* Z, i
     if (nq < 0 || (nq > 0 && !Q) || !Z || !gram || !flags || !any_flag || cond < -1 || cond > 1 ||
         (b != 8 && (!xinv || !F)))
       return N2V2R_ERR_BAD_ARG;
-    Eig eig{};
+    Eig eig(h);
     if (const int s = diag_eig(h, b, nq + 1, eig)) return s;
     if (const int s = diag_gram_info(eig, nq + 1, 1, info)) return s;
     const int c = nq * b;

@@ -1,5 +1,5 @@
 """One application W = M X = sum_k A_k (A_k^T X) as the solver launches it (``n2v2r_gram_apply``:
-an ``Eig`` set up as a fit's, its own ``apply_M``) against fp64 products from scipy / numpy, in
+a ``GramOp`` set up as a fit's, its own ``apply``) against fp64 products from scipy / numpy, in
 every form the operator takes: the row kernels with all layers in one launch, sum mode and the
 XCD split (K up to 8), the flat tiled form with K > 1, the dense GEMMs' accumulation over layers,
 and on a row partition the gather form and the (chunked) reduce-scatter form.
