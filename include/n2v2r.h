@@ -214,6 +214,25 @@ enum { N2V2R_CORR_UNSIGNED = 0, N2V2R_CORR_SIGNED = 1, N2V2R_CORR_SIGNED_HYBRID 
        N2V2R_CORR_RAW = 3 };
 int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples,
                          const double* E /* n x samples, row-major */, int kind, double power);
+/* connectivities for a soft-threshold scan (WGCNA's pickSoftThreshold, hdWGCNA's TestSoftPowers):
+ * for the n x samples expression matrix E of n2v2r_set_layer_corr and n_powers candidate
+ * exponents,
+ *   conn[q][i] = sum_{j != i} pow(t(r_ij), powers[q]),
+ * r and t (N2V2R_CORR_UNSIGNED, _SIGNED or _SIGNED_HYBRID) as n2v2r_set_layer_corr evaluates them,
+ * summed in fp64: the fp64 row sums, diagonal excluded, of exactly the values that call rounds to
+ * fp32 at power powers[q].  E is uploaded (8 n samples bytes) and standardised, every power is
+ * applied to an entry of the fp64 MFMA product while its tile is on the chip and the rows are
+ * summed there; nothing n x n is written on the host or in HBM, and 8 n_powers n bytes come back.
+ * The result is deterministic (no atomics; a function of E, kind and powers alone).  The call
+ * works in device buffers of its own: the handle's layers, embedding and storage are untouched,
+ * and n need not be the handle's node count.  On a multi-GPU handle it runs on rank 0's GPU, on a
+ * rank handle on its own, with no collective.
+ * conn: n_powers x n, row-major.  N2V2R_ERR_BAD_ARG, with the handle usable afterwards: NULL
+ * pointers, n < 1, samples < 2, n_powers outside [1, 32], a power not finite or < 1,
+ * N2V2R_CORR_RAW (r may be negative) or an unknown kind, or a row of E that holds a non-finite
+ * value or is constant (the message names the smallest such row). */
+int n2v2r_soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                            int kind, const double* powers, int n_powers, double* conn);
 /* network_transform (preprocessing_utils.py:116-141) of a loaded DENSE-storage layer, in place in
  * HBM, whichever call loaded it (n2v2r_set_layer_corr or n2v2r_set_layer_dense): the layer never
  * visits the host.  With a = the stored fp32 values (as fp64, which is exact):

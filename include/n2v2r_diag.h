@@ -228,6 +228,17 @@ int n2v2r_bench_transform_pass(n2v2r_handle* h, int k, int which, int flags, dou
  * lda = 64 ceil(n / 64) (about n^3). */
 int n2v2r_bench_tom_tiles(n2v2r_handle* h, int k, int type, int reps, double* ms, double* flop);
 
+/* n2v2r_soft_connectivity with the chunk count given (tests, tools/soft_threshold_probe.py):
+ * every tile row's tile columns are split into `chunks` contiguous chunks, one workgroup and one
+ * partial sum each, added in ascending order (0: the count the call itself takes, a function of n
+ * alone; at most ceil(n / 64)).  chunks_used (optional) = the count that ran; kernel_ms (optional)
+ * = soft_conn_kernel's time, one HIP event pair on the engine stream around its one launch (the
+ * upload, the standardisation and the chunk sum are outside it).  Errors as
+ * n2v2r_soft_connectivity, and N2V2R_ERR_BAD_ARG for chunks outside [0, ceil(n / 64)]. */
+int n2v2r_soft_connectivity_chunks(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                                   int kind, const double* powers, int n_powers, int chunks,
+                                   double* conn, int* chunks_used, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

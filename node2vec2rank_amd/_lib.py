@@ -14,7 +14,7 @@ import weakref
 
 import numpy as np
 
-from .coexpression import Coexpression
+from .coexpression import KINDS, Coexpression
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("N2V2R_LIB", os.path.join(_HERE, "lib", "libn2v2r_hip.so"))
@@ -55,7 +55,8 @@ EXPORTED = [
     "n2v2r_bench_transform_pass", "n2v2r_tom_layer", "n2v2r_bench_tom_tiles", "n2v2r_pip_pass",
     "n2v2r_gram_apply", "n2v2r_ritz_step", "n2v2r_layers_to_csr", "n2v2r_count_layer_nonzeros",
     "n2v2r_get_layer_csr_nnz", "n2v2r_get_layer_csr", "n2v2r_bench_sparsify_pass",
-    "n2v2r_block_gram", "n2v2r_ortho_pass",
+    "n2v2r_block_gram", "n2v2r_ortho_pass", "n2v2r_soft_connectivity",
+    "n2v2r_soft_connectivity_chunks",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -226,6 +227,12 @@ def load(path: str | None = None):
                                          _p(np.float32)]),
             "n2v2r_bench_sparsify_pass": (_i, [_vp, _i, _i, _i, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]),
+            "n2v2r_soft_connectivity": (_i, [_vp, _i64, _i64, _p(np.float64), _i, _p(np.float64),
+                                             _i, _p(np.float64)]),
+            "n2v2r_soft_connectivity_chunks": (_i, [_vp, _i64, _i64, _p(np.float64), _i,
+                                                    _p(np.float64), _i, _i, _p(np.float64),
+                                                    ctypes.POINTER(_i),
+                                                    ctypes.POINTER(ctypes.c_double)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -806,6 +813,45 @@ class Engine:
         out = np.empty((k, k), dtype=np.float64)
         self._check(self.lib.n2v2r_project(self.h, m, n, W, int(oc), out), "project")
         return out
+
+    def _soft_args(self, E, kind, powers):
+        values = getattr(E, "values", E)  # (a DataFrame's array)
+        try:
+            e = np.ascontiguousarray(np.asarray(values), dtype=np.float64)
+            pw = np.ascontiguousarray(np.asarray(powers), dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"expression and powers must be real arrays: {err}") from None
+        if e.ndim != 2:
+            raise ValueError(f"expression must be 2-D (n x samples), got {e.ndim}-D")
+        if not isinstance(kind, str) or kind.replace("_", " ").casefold() not in KINDS:
+            raise ValueError(f"unknown kind {kind!r}; options are {sorted(KINDS)}")
+        return e, KINDS[kind.replace("_", " ").casefold()], pw
+
+    def soft_connectivity(self, E, kind: str = "unsigned", powers=(6.0,)):
+        """Connectivities for a soft-threshold scan (n2v2r_soft_connectivity): for the
+        ``n x samples`` expression matrix E and each candidate power p, ``k_i(p) = sum_{j != i}
+        t(r_ij) ** p`` with r and t as a ``Coexpression`` layer of that kind evaluates them, summed
+        in fp64 on the GPU without an n x n array anywhere.  Returns ``(len(powers), n)`` float64.
+        The loaded layers, the embedding and ``storage`` stay as they are.  ``ValueError``: fewer
+        than 2 samples, more than 32 powers, a power not finite or < 1, kind ``"raw"`` or
+        unknown, a row of E that is constant or holds a non-finite value (named by index)."""
+        e, kid, pw = self._soft_args(E, kind, powers)
+        out = np.empty((pw.size, e.shape[0]), dtype=np.float64)
+        self._check(self.lib.n2v2r_soft_connectivity(self.h, e.shape[0], e.shape[1], e, kid, pw,
+                                                     int(pw.size), out), "soft_connectivity")
+        return out
+
+    def soft_connectivity_chunks(self, E, kind: str = "unsigned", powers=(6.0,), chunks: int = 0):
+        """``soft_connectivity`` with the chunk count of the scan given (0: the call's own) and
+        the scan kernel timed (n2v2r_soft_connectivity_chunks).  Returns (the connectivities, the
+        chunk count that ran, the scan kernel's ms from one HIP event pair)."""
+        e, kid, pw = self._soft_args(E, kind, powers)
+        out = np.empty((pw.size, e.shape[0]), dtype=np.float64)
+        used, ms = _i(), ctypes.c_double()
+        self._check(self.lib.n2v2r_soft_connectivity_chunks(
+            self.h, e.shape[0], e.shape[1], e, kid, pw, int(pw.size), int(chunks), out,
+            ctypes.byref(used), ctypes.byref(ms)), "soft_connectivity_chunks")
+        return out, used.value, ms.value
 
     def rr_top(self, H, p: int):
         """Rayleigh-Ritz stage alone: top-p eigenpairs of symmetric H (GPU tridiagonalisation,

@@ -18,11 +18,11 @@ _TAG = os.environ.get("N2V2R_BUILD_TAG", "")
 LIB = os.path.join(OUT_DIR, f"libn2v2r_hip_{_TAG}.so" if _TAG else "libn2v2r_hip.so")
 OBJ_DIR = os.path.join(OUT_DIR, f"obj_{_TAG}" if _TAG else "obj")
 
-HIP_SOURCES = ["spmm.hip", "dense.hip", "gemm.hip", "corr.hip", "tom.hip", "transform.hip", "sparsify.hip", "rank.hip",
+HIP_SOURCES = ["spmm.hip", "dense.hip", "gemm.hip", "corr.hip", "soft_threshold.hip", "tom.hip", "transform.hip", "sparsify.hip", "rank.hip",
                "rr.hip", "rr_band.hip", "rr_sturm.hip", "ingest.hip", "engine.cpp", "layers.cpp",
                "comm.cpp", "gram_op.cpp", "solver.cpp", "ranking.cpp", "multi.cpp"]
 HOST_SOURCES: list = []
-HEADERS = ["common.h", "pip_pass.h", "spmm_args.h", "engine.h", "gram_op.h", os.path.join("..", "..", "include", "n2v2r.h"),
+HEADERS = ["common.h", "corr_tile.h", "pip_pass.h", "spmm_args.h", "engine.h", "gram_op.h", os.path.join("..", "..", "include", "n2v2r.h"),
            os.path.join("..", "..", "include", "n2v2r_diag.h")]
 ARCH = os.environ.get("N2V2R_OFFLOAD_ARCH", "gfx950")
 # probe builds only (with N2V2R_BUILD_TAG): extra -D flags for the HIP sources

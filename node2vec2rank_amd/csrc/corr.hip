@@ -40,12 +40,7 @@
 #include <cstdint>
 
 #include "common.h"
-
-#define CORR_KC 16            // k per LDS round; Z's row pitch sp is a multiple of it
-#define CORR_ZP (CORR_KC + 2)  // LDS row pitch of an operand tile, in doubles (see above)
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+#include "corr_tile.h"
 
 __global__ __launch_bounds__(256) void corr_standardise_kernel(const double* __restrict__ E,
                                                                int64_t n, int64_t s,
@@ -89,27 +84,9 @@ __global__ __launch_bounds__(256) void corr_standardise_kernel(const double* __r
   for (int64_t k = lane; k < sp; k += 64) z[k] = (ok && k < s) ? (e[k] - mean) / norm : 0.0;
 }
 
-__device__ __forceinline__ void corr_load(const double* __restrict__ Z, int64_t sp, int64_t i0,
-                                          int64_t j0, int64_t k0, f64x2 (&va)[2],
-                                          f64x2 (&vb)[2]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int64_t off = (int64_t)((t >> 3) + 32 * u) * sp + k0 + 2 * (t & 7);
-    va[u] = *reinterpret_cast<const f64x2*>(Z + i0 * sp + off);
-    vb[u] = *reinterpret_cast<const f64x2*>(Z + j0 * sp + off);
-  }
-}
-
 // kind: N2V2R_CORR_* (include/n2v2r.h)
 __device__ __forceinline__ float corr_entry(double c, int kind, double power) {
-  const double r = fmin(fmax(c, -1.0), 1.0);
-  double t = r;                                // raw
-  if (kind == 0) t = fabs(r);                  // unsigned
-  else if (kind == 1) t = (1.0 + r) * 0.5;     // signed
-  else if (kind == 2) t = fmax(r, 0.0);        // signed hybrid
-  if (power != 1.0) t = pow(t, power);
-  return (float)t;
+  return (float)corr_value(c, kind, power);
 }
 
 __global__ __launch_bounds__(256) void corr_tile_kernel(const double* __restrict__ Z, int64_t sp,
@@ -133,27 +110,10 @@ __global__ __launch_bounds__(256) void corr_tile_kernel(const double* __restrict
   corr_load(Z, sp, i0, j0, 0, va, vb);
   for (int64_t k0 = 0; k0 < sp; k0 += CORR_KC) {
     __syncthreads();  // the previous round's LDS reads are done
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      *reinterpret_cast<f64x2*>(&za[(tid >> 3) + 32 * u][2 * (tid & 7)]) = va[u];
-      *reinterpret_cast<f64x2*>(&zb[(tid >> 3) + 32 * u][2 * (tid & 7)]) = vb[u];
-    }
+    corr_stage(za, zb, va, vb);
     __syncthreads();
     if (k0 + CORR_KC < sp) corr_load(Z, sp, i0, j0, k0 + CORR_KC, va, vb);
-#pragma unroll
-    for (int ks = 0; ks < CORR_KC; ks += 4) {
-      double av[2], bv[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        av[t] = za[wi + t * 16 + (lane & 15)][ks + (lane >> 4)];
-        bv[t] = zb[wj + t * 16 + (lane & 15)][ks + (lane >> 4)];
-      }
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
-    }
+    corr_mfma_round(za, zb, wi, wj, lane, acc);
   }
   // f64 16x16x4 C/D map: col = lane & 15, row = (lane >> 4) + 4 * reg
 #pragma unroll

@@ -127,6 +127,13 @@ hipError_t n2v2r_launch_corr_standardise(const double* E, int64_t n, int64_t s, 
 hipError_t n2v2r_launch_corr_tiles(const double* Z, int64_t s, int64_t n, int64_t row0,
                                    int64_t nloc, float* A, int64_t lda, int kind, double power,
                                    hipStream_t stream);
+// soft_threshold.hip: connectivities of a soft-threshold scan from the standardised rows Z
+int n2v2r_soft_chunks(int64_t n);
+hipError_t n2v2r_launch_soft_conn(const double* Z, int64_t s, int64_t n, int kind,
+                                  const double* powers, int P, int G, double* part,
+                                  hipStream_t stream);
+hipError_t n2v2r_launch_soft_conn_sum(const double* part, int G, int P, int64_t n, double* conn,
+                                      hipStream_t stream);
 // tom.hip: topological overlap of a symmetric dense layer.  A: all n rows of the layer (n x lda
 // fp32); type: N2V2R_TOM_*
 hipError_t n2v2r_launch_tom_check(const float* A, int64_t rows, int64_t lda, int64_t n, int type,

@@ -1394,4 +1394,115 @@ int n2v2r_project(n2v2r_handle* h, int64_t m, int64_t n, const double* W, int on
   });
 }
 
+// Soft-threshold scan (soft_threshold.hip): E is uploaded whole and standardised as
+// n2v2r_set_layer_corr does it, the scan kernel writes one partial per chunk and a second kernel
+// adds them.  Every buffer is local to the call; nothing of the handle but its stream is used.
+// chunks: 0 = n2v2r_soft_chunks(n); ms (optional): the scan kernel's time from one event pair.
+static int soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                             int kind, const double* powers, int n_powers, int chunks,
+                             double* conn, int* chunks_used, double* ms) {
+  if (h && h->multi()) h = h->ranks[0];  // no collective: rank 0's GPU
+  return guarded(h, [&]() -> int {
+    if (!E || !powers || !conn || n < 1 || n > 0x7fffffffLL) {
+      h->set_err("soft_connectivity: E, powers and conn must be given and 1 <= n < 2^31");
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (samples < 2) {
+      h->set_err("soft_connectivity: a correlation needs at least 2 samples, got %lld",
+                 (long long)samples);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (n_powers < 1 || n_powers > 32) {
+      h->set_err("soft_connectivity: between 1 and 32 powers per call, got %d", n_powers);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    for (int q = 0; q < n_powers; ++q)
+      if (!std::isfinite(powers[q]) || powers[q] < 1.0) {
+        h->set_err("soft_connectivity: power must be finite and >= 1, got %g (powers[%d])",
+                   powers[q], q);
+        return N2V2R_ERR_BAD_ARG;
+      }
+    if (kind == N2V2R_CORR_RAW) {
+      h->set_err("soft_connectivity: a raw correlation takes no power (r may be negative): the "
+                 "kinds are unsigned, signed and signed hybrid");
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (kind != N2V2R_CORR_UNSIGNED && kind != N2V2R_CORR_SIGNED &&
+        kind != N2V2R_CORR_SIGNED_HYBRID) {
+      h->set_err("soft_connectivity: unknown correlation kind %d", kind);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    const int64_t nt = (n + 63) / 64, npad = nt * 64, sp = n2v2r_corr_spad(samples);
+    if (chunks < 0 || chunks > nt || chunks > 65535) {
+      h->set_err("soft_connectivity: chunks must lie in [0, %lld], got %d", (long long)nt, chunks);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    const int G = chunks ? chunks : n2v2r_soft_chunks(n);
+    hipStream_t st = h->stream;
+    DevBuf e, z, pw, flag, part, out;  // (the kernels write every element that is read)
+    e.ensure_raw(sizeof(double) * n * samples);
+    z.ensure_raw(sizeof(double) * npad * sp);
+    pw.ensure_raw(sizeof(double) * 32);
+    flag.ensure_raw(sizeof(unsigned) * 4);
+    part.ensure_raw(sizeof(double) * G * n_powers * npad);
+    out.ensure_raw(sizeof(double) * n_powers * n);
+    HIPCHK(hipMemcpyAsync(e.p, E, sizeof(double) * n * samples, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pw.p, powers, sizeof(double) * n_powers, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(flag.p, 0xFF, sizeof(unsigned), st));
+    HIPCHK(n2v2r_launch_corr_standardise(e.as<double>(), n, samples, z.as<double>(),
+                                         flag.as<unsigned>(), st));
+    unsigned bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad != 0xFFFFFFFFu) {
+      h->set_err("soft_connectivity: row %u of the expression matrix holds a non-finite value or "
+                 "is constant (zero variance): its correlations are undefined", bad);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ms) {
+      HIPCHK(hipEventCreate(&e0));
+      const hipError_t ce = hipEventCreate(&e1);
+      if (ce != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        throw HipFail{ce, "hipEventCreate"};
+      }
+    }
+    hipError_t err = hipSuccess;
+    if (ms) err = hipEventRecord(e0, st);
+    if (err == hipSuccess)
+      err = n2v2r_launch_soft_conn(z.as<double>(), samples, n, kind, pw.as<double>(), n_powers, G,
+                                   part.as<double>(), st);
+    if (ms && err == hipSuccess) err = hipEventRecord(e1, st);
+    if (err == hipSuccess)
+      err = n2v2r_launch_soft_conn_sum(part.as<double>(), G, n_powers, n, out.as<double>(), st);
+    if (err == hipSuccess)
+      err = hipMemcpyAsync(conn, out.p, sizeof(double) * n_powers * n, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // the local buffers die here
+    float t = 0.f;
+    if (ms && err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+    if (ms) {
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+    }
+    if (err != hipSuccess) throw HipFail{err, "soft_connectivity"};
+    if (ms) *ms = (double)t;
+    if (chunks_used) *chunks_used = G;
+    return N2V2R_OK;
+  });
+}
+
+int n2v2r_soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const double* E, int kind,
+                            const double* powers, int n_powers, double* conn) {
+  return soft_connectivity(h, n, samples, E, kind, powers, n_powers, 0, conn, nullptr, nullptr);
+}
+
+// diagnostics (n2v2r_diag.h): the scan with the chunk count given, the scan kernel timed
+int n2v2r_soft_connectivity_chunks(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                                   int kind, const double* powers, int n_powers, int chunks,
+                                   double* conn, int* chunks_used, double* kernel_ms) {
+  return soft_connectivity(h, n, samples, E, kind, powers, n_powers, chunks, conn, chunks_used,
+                           kernel_ms);
+}
+
 }  // extern "C"
