@@ -233,6 +233,39 @@ int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples,
  * value or is constant (the message names the smallest such row). */
 int n2v2r_soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
                             int kind, const double* powers, int n_powers, double* conn);
+/* the correlation behind a co-expression layer or a soft-threshold scan.  All three are Z Z^T of
+ * differently standardised rows; the fp64 MFMA product, the kind's map, the power and every later
+ * stage (TOM, transform, CSR conversion) are the same.
+ *   N2V2R_COR_PEARSON   rows centred by their mean, divided by their centred 2-norm: the two
+ *     calls above, with the same kernels in the same order and the same bits.
+ *   N2V2R_COR_SPEARMAN  the Pearson correlation of the rows' average ranks: element i of a row
+ *     gets rank #{j : x_j < x_i} + (#{j : x_j == x_i} + 1) / 2 (1-based; ties share their mean
+ *     rank, as scipy.stats.rankdata(method="average") and R's rank(); -0.0 and +0.0 tie), an
+ *     exact half-integer in fp64, and the rank matrix is standardised by the Pearson kernel: the
+ *     layer equals, bit for bit, the N2V2R_COR_PEARSON layer of the rank matrix.
+ *   N2V2R_COR_BICOR     the biweight midcorrelation, WGCNA's bicor with maxPOutliers = 1 and
+ *     pearsonFallback = "individual".  Per row x, in fp64: med = median(x) (the middle order
+ *     statistic, or (a + b) / 2 of the two middle ones: np.median), c = x - med, mad = median(|c|)
+ *     (the raw MAD, no 1.4826), u = c / (9 mad), w = (1 - u^2)^2 where |u| < 1 and 0 elsewhere,
+ *     a = c w, z = a / sqrt(sum a^2).  A row with mad == 0 (at least half of its values equal its
+ *     median) has no robust scale: it is standardised by the Pearson formula instead, bit for bit
+ *     as N2V2R_COR_PEARSON standardises it, and counted.
+ * fallback (optional, 2 values out): fallback[0] = the rows that took that Pearson fallback (0 for
+ * the other methods), fallback[1] = the smallest such row, or -1.  On a partitioned or multi-GPU
+ * handle every rank standardises all of E; rank 0's counts are returned.
+ * A row that holds a non-finite value (+-inf too, under every method: its rank would be defined,
+ * but there is one rule) or is constant is refused as by the calls above.  An unknown method is
+ * N2V2R_ERR_BAD_ARG; every other refusal of the calls above applies unchanged, a refused
+ * n2v2r_set_layer_corr_method leaves the layer unloaded and the handle usable.
+ * Out of scope: maxPOutliers < 1, pearsonFallback = "all" or "none", missing values
+ * (use = "pairwise.complete.obs") and Kendall's tau. */
+enum { N2V2R_COR_PEARSON = 0, N2V2R_COR_SPEARMAN = 1, N2V2R_COR_BICOR = 2 };
+int n2v2r_set_layer_corr_method(n2v2r_handle* h, int k, int64_t n, int64_t samples,
+                                const double* E /* n x samples, row-major */, int kind,
+                                double power, int method, int64_t* fallback /* optional, 2 out */);
+int n2v2r_soft_connectivity_method(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                                   int kind, const double* powers, int n_powers, int method,
+                                   double* conn, int64_t* fallback /* optional, 2 out */);
 /* network_transform (preprocessing_utils.py:116-141) of a loaded DENSE-storage layer, in place in
  * HBM, whichever call loaded it (n2v2r_set_layer_corr or n2v2r_set_layer_dense): the layer never
  * visits the host.  With a = the stored fp32 values (as fp64, which is exact):

@@ -239,6 +239,28 @@ int n2v2r_soft_connectivity_chunks(n2v2r_handle* h, int64_t n, int64_t samples, 
                                    int kind, const double* powers, int n_powers, int chunks,
                                    double* conn, int* chunks_used, double* kernel_ms);
 
+/* The row passes of the correlation methods (N2V2R_COR_*, n2v2r.h) apart from the tile product
+ * (tests, tools/cor_method_probe.py).  Each call uploads E (n x samples, row-major fp64) into
+ * buffers of its own on the engine stream and leaves the handle as it is; on a multi-GPU handle it
+ * runs on rank 0's GPU, with no collective.  N2V2R_ERR_BAD_ARG: NULL E or output, n < 1,
+ * samples < 2, an unknown method.
+ * n2v2r_corr_ranks: R (n x samples) = the per-row average ranks corr_rank_kernel writes, exact
+ * half-integers; a row that holds a non-finite value comes back as NaNs (the standardisation that
+ * follows refuses it).
+ * n2v2r_corr_standardise: Z (n x samples) = columns [0, samples) of rows [0, n) of the
+ * standardised rows the tile product consumes, under `method`; bad_row (optional) = the smallest
+ * row that holds a non-finite value or is constant, or -1.  A bad row is no error here: its Z is
+ * zeros.
+ * n2v2r_bench_corr_rows: the method's row kernel alone (N2V2R_COR_PEARSON: corr_standardise_kernel,
+ * N2V2R_COR_SPEARMAN: corr_rank_kernel, N2V2R_COR_BICOR: corr_bicor_kernel), launched 1 + reps
+ * times (the first is a warm-up), each between its own HIP event pair; ms[0 .. reps). */
+int n2v2r_corr_ranks(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                     double* R /* n x samples */);
+int n2v2r_corr_standardise(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                           int method, double* Z /* n x samples */, int64_t* bad_row);
+int n2v2r_bench_corr_rows(n2v2r_handle* h, int64_t n, int64_t samples, const double* E, int method,
+                          int reps, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,11 +10,12 @@ import atexit
 import ctypes
 import os
 import threading
+import warnings
 import weakref
 
 import numpy as np
 
-from .coexpression import KINDS, Coexpression
+from .coexpression import KINDS, METHODS, Coexpression, method_name
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("N2V2R_LIB", os.path.join(_HERE, "lib", "libn2v2r_hip.so"))
@@ -56,7 +57,9 @@ EXPORTED = [
     "n2v2r_gram_apply", "n2v2r_ritz_step", "n2v2r_layers_to_csr", "n2v2r_count_layer_nonzeros",
     "n2v2r_get_layer_csr_nnz", "n2v2r_get_layer_csr", "n2v2r_bench_sparsify_pass",
     "n2v2r_block_gram", "n2v2r_ortho_pass", "n2v2r_soft_connectivity",
-    "n2v2r_soft_connectivity_chunks",
+    "n2v2r_soft_connectivity_chunks", "n2v2r_set_layer_corr_method",
+    "n2v2r_soft_connectivity_method", "n2v2r_corr_ranks", "n2v2r_corr_standardise",
+    "n2v2r_bench_corr_rows",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -122,6 +125,15 @@ class TransformStats(ctypes.Structure):
 TF_ABSOLUTE, TF_BINARIZE, TF_THRESHOLD = 1, 2, 4
 # n2v2r_tom_layer types: N2V2R_TOM_*
 TOM_KINDS = {"unsigned": 0, "signed": 1}
+
+
+def _warn_zero_mad(what, fallback):
+    """The RuntimeWarning of a bicor build in which rows took the Pearson fallback."""
+    if int(fallback[0]) > 0:
+        warnings.warn(f"{what}: {int(fallback[0])} rows have zero MAD (first: row "
+                      f"{int(fallback[1])}); Pearson standardisation used for them",
+                      RuntimeWarning, stacklevel=3)
+
 
 _lib = None
 _lock = threading.RLock()  # re-entered: acquire_engine -> Engine() -> load()
@@ -233,6 +245,16 @@ def load(path: str | None = None):
                                                     _p(np.float64), _i, _i, _p(np.float64),
                                                     ctypes.POINTER(_i),
                                                     ctypes.POINTER(ctypes.c_double)]),
+            "n2v2r_set_layer_corr_method": (_i, [_vp, _i, _i64, _i64, _p(np.float64), _i,
+                                                 ctypes.c_double, _i, _vp]),
+            "n2v2r_soft_connectivity_method": (_i, [_vp, _i64, _i64, _p(np.float64), _i,
+                                                    _p(np.float64), _i, _i, _p(np.float64),
+                                                    _vp]),
+            "n2v2r_corr_ranks": (_i, [_vp, _i64, _i64, _p(np.float64), _p(np.float64)]),
+            "n2v2r_corr_standardise": (_i, [_vp, _i64, _i64, _p(np.float64), _i, _p(np.float64),
+                                            ctypes.POINTER(_i64)]),
+            "n2v2r_bench_corr_rows": (_i, [_vp, _i64, _i64, _p(np.float64), _i, _i,
+                                           _p(np.float64)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -408,7 +430,9 @@ class Engine:
     def set_layers(self, layers, symmetric=SYM_DETECT, storage="auto", sparsify=False):
         """layers: list of scipy.sparse matrices (any format) or dense arrays, N x N, or
         ``Coexpression`` layers (an N x samples expression matrix each: the engine builds the
-        N x N co-expression layer on the GPU, n2v2r_set_layer_corr).
+        N x N co-expression layer on the GPU, n2v2r_set_layer_corr; a layer whose ``method`` is
+        not Pearson goes through n2v2r_set_layer_corr_method, and a bicor layer in which rows
+        have zero MAD raises a ``RuntimeWarning`` with their count and the first of them).
 
         storage: "csr", "dense" (fp32 N x N in HBM, MFMA GEMMs) or "auto" (dense when every
         layer is a dense array with more than 1/4 of its entries non-zero).  A list that holds a
@@ -453,12 +477,18 @@ class Engine:
                     raise ValueError("all layers must be square and share the node set")
             self._check(self.lib.n2v2r_set_num_layers(self.h, len(arrs), n), "set_num_layers")
             for k, a in enumerate(arrs):
-                if isinstance(a, Coexpression):
+                fallback = np.array([0, -1], dtype=np.int64)
+                if isinstance(a, Coexpression) and a.method != "pearson":
+                    st = self.lib.n2v2r_set_layer_corr_method(
+                        self.h, k, n, a.expression.shape[1], a.expression, a.kind_id, a.power,
+                        a.method_id, fallback.ctypes.data_as(_vp))
+                elif isinstance(a, Coexpression):
                     st = self.lib.n2v2r_set_layer_corr(self.h, k, n, a.expression.shape[1],
                                                        a.expression, a.kind_id, a.power)
                 else:
                     st = self.lib.n2v2r_set_layer_dense(self.h, k, n, a, int(symmetric))
                 self._check(st, f"layer {k}")
+                _warn_zero_mad(f"layer {k}", fallback)
                 # WGCNA's order (adjacency, then its topological overlap), then the reference's
                 # network_transform
                 if isinstance(a, Coexpression) and a.tom is not None:
@@ -827,19 +857,77 @@ class Engine:
             raise ValueError(f"unknown kind {kind!r}; options are {sorted(KINDS)}")
         return e, KINDS[kind.replace("_", " ").casefold()], pw
 
-    def soft_connectivity(self, E, kind: str = "unsigned", powers=(6.0,)):
+    def soft_connectivity(self, E, kind: str = "unsigned", powers=(6.0,),
+                          method: str = "pearson"):
         """Connectivities for a soft-threshold scan (n2v2r_soft_connectivity): for the
         ``n x samples`` expression matrix E and each candidate power p, ``k_i(p) = sum_{j != i}
         t(r_ij) ** p`` with r and t as a ``Coexpression`` layer of that kind evaluates them, summed
         in fp64 on the GPU without an n x n array anywhere.  Returns ``(len(powers), n)`` float64.
         The loaded layers, the embedding and ``storage`` stay as they are.  ``ValueError``: fewer
         than 2 samples, more than 32 powers, a power not finite or < 1, kind ``"raw"`` or
-        unknown, a row of E that is constant or holds a non-finite value (named by index)."""
+        unknown, a row of E that is constant or holds a non-finite value (named by index).
+
+        method: ``"pearson"``, ``"spearman"`` or ``"bicor"`` (n2v2r_soft_connectivity_method), the
+        correlation r as a ``Coexpression`` layer of that method evaluates it; a bicor scan in
+        which rows have zero MAD raises the ``RuntimeWarning`` ``set_layers`` raises."""
         e, kid, pw = self._soft_args(E, kind, powers)
+        mid = METHODS[method_name(method)]
         out = np.empty((pw.size, e.shape[0]), dtype=np.float64)
-        self._check(self.lib.n2v2r_soft_connectivity(self.h, e.shape[0], e.shape[1], e, kid, pw,
-                                                     int(pw.size), out), "soft_connectivity")
+        if mid == 0:
+            self._check(self.lib.n2v2r_soft_connectivity(self.h, e.shape[0], e.shape[1], e, kid,
+                                                         pw, int(pw.size), out),
+                        "soft_connectivity")
+            return out
+        fallback = np.array([0, -1], dtype=np.int64)
+        self._check(self.lib.n2v2r_soft_connectivity_method(
+            self.h, e.shape[0], e.shape[1], e, kid, pw, int(pw.size), mid, out,
+            fallback.ctypes.data_as(_vp)), "soft_connectivity")
+        _warn_zero_mad("soft_connectivity", fallback)
         return out
+
+    def _rows_arg(self, E):
+        values = getattr(E, "values", E)  # (a DataFrame's array)
+        try:
+            e = np.ascontiguousarray(np.asarray(values), dtype=np.float64)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"expression must be a real n x samples array: {err}") from None
+        if e.ndim != 2:
+            raise ValueError(f"expression must be 2-D (n x samples), got {e.ndim}-D")
+        return e
+
+    def corr_ranks(self, E):
+        """The per-row average ranks of E (n x samples) as the Spearman path computes them on the
+        GPU (n2v2r_corr_ranks): ``scipy.stats.rankdata(E, axis=1)``, exact half-integers in
+        float64; a row that holds a non-finite value comes back as NaNs."""
+        e = self._rows_arg(E)
+        out = np.empty_like(e)
+        self._check(self.lib.n2v2r_corr_ranks(self.h, e.shape[0], e.shape[1], e, out),
+                    "corr_ranks")
+        return out
+
+    def corr_standardise(self, E, method: str = "pearson", return_bad_row: bool = False):
+        """The standardised rows Z (n x samples float64) whose products Z Z^T are the
+        correlations of ``method`` (n2v2r_corr_standardise).  A row that is constant or holds a
+        non-finite value is zeros, not an error; with ``return_bad_row`` the result is
+        ``(Z, the smallest such row or -1)``."""
+        e = self._rows_arg(E)
+        out = np.empty_like(e)
+        bad = _i64()
+        self._check(self.lib.n2v2r_corr_standardise(self.h, e.shape[0], e.shape[1], e,
+                                                    METHODS[method_name(method)], out,
+                                                    ctypes.byref(bad)), "corr_standardise")
+        return (out, int(bad.value)) if return_bad_row else out
+
+    def bench_corr_rows(self, E, method: str = "pearson", reps: int = 10):
+        """The row kernel of ``method`` alone (Pearson: the standardisation, Spearman: the
+        ranking, bicor: its standardisation), ``reps`` launches after a warm-up, one HIP event
+        pair each (n2v2r_bench_corr_rows).  Returns the times in ms."""
+        e = self._rows_arg(E)
+        ms = np.empty(int(reps), dtype=np.float64)
+        self._check(self.lib.n2v2r_bench_corr_rows(self.h, e.shape[0], e.shape[1], e,
+                                                   METHODS[method_name(method)], int(reps), ms),
+                    "bench_corr_rows")
+        return ms
 
     def soft_connectivity_chunks(self, E, kind: str = "unsigned", powers=(6.0,), chunks: int = 0):
         """``soft_connectivity`` with the chunk count of the scan given (0: the call's own) and

@@ -14,10 +14,20 @@ import numpy as np
 KINDS = {"unsigned": 0, "signed": 1, "signed hybrid": 2, "raw": 3}
 # tom -> N2V2R_TOM_*; the names follow WGCNA's TOMType
 TOMS = ("unsigned", "signed")
+# method -> N2V2R_COR_* (include/n2v2r.h); the names follow R's cor(method=) and WGCNA's corFnc
+METHODS = {"pearson": 0, "spearman": 1, "bicor": 2}
+
+
+def method_name(method) -> str:
+    """The case-folded name of a correlation method; ``ValueError`` for anything else."""
+    if not isinstance(method, str) or method.casefold() not in METHODS:
+        raise ValueError(f"unknown method {method!r}; options are {sorted(METHODS)}")
+    return method.casefold()
 
 
 class Coexpression:
-    """One layer: ``t(np.corrcoef(expression)) ** power`` over the rows of ``expression``.
+    """One layer: ``t(np.corrcoef(expression)) ** power`` over the rows of ``expression`` (or
+    the Spearman or biweight midcorrelation in ``np.corrcoef``'s place, see ``method``).
 
     expression: ``n x samples`` (n nodes / genes), any real dtype or a DataFrame; kept as a
         C-contiguous float64 array (``.expression``).
@@ -36,13 +46,21 @@ class Coexpression:
         ``top_percent_keep`` percent of the non-zero entries stay (an ``np.percentile`` cut), and
         with ``binarize`` the survivors become 1.  The defaults (``None``, 100, ``False``) leave
         the layer as built.  There is no ``absolute`` option: ``kind="unsigned"`` is that.
+    method: the correlation r, case-folded.  ``"pearson"`` (the default); ``"spearman"``, the
+        Pearson correlation of the rows' average ranks (ties share their mean rank, as
+        ``scipy.stats.rankdata``); ``"bicor"``, the biweight midcorrelation, WGCNA's
+        ``corFnc = "bicor"`` with ``maxPOutliers = 1`` and ``pearsonFallback = "individual"``: a
+        row whose MAD is zero is standardised by the Pearson formula, and the engine warns with
+        the count of such rows.  Missing values, ``maxPOutliers < 1``, the other fallback modes
+        and Kendall's tau are out of scope.
 
     Every violation is a ``ValueError`` here, before any GPU work; rows the correlation is
     undefined for (a non-finite value, zero variance) are reported by the engine when the layer
     is loaded, by row index."""
 
     def __init__(self, expression, kind: str = "unsigned", power: float = 1.0, threshold=None,
-                 top_percent_keep=100, binarize: bool = False, tom=None):
+                 top_percent_keep=100, binarize: bool = False, tom=None,
+                 method: str = "pearson"):
         values = getattr(expression, "values", expression)  # (a DataFrame's array)
         try:
             e = np.ascontiguousarray(np.asarray(values), dtype=np.float64)
@@ -82,6 +100,7 @@ class Coexpression:
             raise ValueError(f"binarize must be True or False, got {binarize!r}")
         if tom is not None and (not isinstance(tom, str) or tom.casefold() not in TOMS):
             raise ValueError(f"unknown tom {tom!r}; options are None, 'unsigned' and 'signed'")
+        self.method = method_name(method)
         self.expression = e
         self.power = p
         self.threshold = threshold
@@ -99,6 +118,10 @@ class Coexpression:
         return KINDS[self.kind]
 
     @property
+    def method_id(self) -> int:
+        return METHODS[self.method]
+
+    @property
     def filters(self) -> bool:
         """Whether any of threshold / top_percent_keep / binarize is set."""
         return self.threshold is not None or self.top_percent_keep != 100.0 or self.binarize
@@ -112,8 +135,10 @@ class Coexpression:
     def __repr__(self):
         n, s = self.expression.shape
         extra = ""
+        if self.method != "pearson":
+            extra = f", method={self.method!r}"
         if self.tom is not None:
-            extra = f", tom={self.tom!r}"
+            extra += f", tom={self.tom!r}"
         if self.filters:
             extra += (f", threshold={self.threshold!r}, top_percent_keep={self.top_percent_keep:g}"
                       f", binarize={self.binarize}")

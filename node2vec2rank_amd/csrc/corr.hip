@@ -8,6 +8,13 @@
 //     [s, sp) and rows [n, npad) zero, so the tile kernel loads without bounds tests).  A bad row
 //     (a non-finite value, or a constant row: zero centred norm) is written as zeros and its index
 //     goes into *bad by atomicMin (the smallest bad row wins, whichever wave gets there first).
+//   corr_rank_kernel  (Spearman) one wave per row: E -> its per-row average ranks R, ties sharing
+//     their mean rank (scipy.stats.rankdata, R's rank()), by a counting pass over the row in LDS;
+//     corr_standardise_kernel then takes R for E: Spearman's Z is Pearson's Z of the ranks.
+//   corr_bicor_kernel  (biweight midcorrelation, WGCNA's bicor with maxPOutliers = 1) one wave
+//     per row: median and raw MAD selected from the same counts, rows centred by the median and
+//     weighted by (1 - u^2)^2, u = (x - med) / (9 MAD), |u| < 1, normalised -> Z in the same
+//     layout; a row with MAD = 0 takes the Pearson row (pearsonFallback = "individual").
 //   corr_tile_kernel  C = Z Z^T by v_mfma_f64_16x16x4_f64 over 64 x 64 tiles, as syrk_f64_kernel
 //     (gemm.hip): four waves, each a 32 x 32 quarter as 2 x 2 MFMA tiles, 16 k per LDS round.  Z
 //     is k-contiguous per row, so a round's 64 x 16 operand tile is loaded as 16-B pieces, 8 lanes
@@ -42,20 +49,12 @@
 #include "common.h"
 #include "corr_tile.h"
 
-__global__ __launch_bounds__(256) void corr_standardise_kernel(const double* __restrict__ E,
-                                                               int64_t n, int64_t s,
-                                                               double* __restrict__ Z, int64_t sp,
-                                                               int64_t npad,
-                                                               unsigned* __restrict__ bad) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= npad) return;  // (wave-uniform)
-  double* z = Z + r * sp;
-  if (r >= n) {
-    for (int64_t k = lane; k < sp; k += 64) z[k] = 0.0;
-    return;
-  }
-  const double* e = E + r * s;
+// Row r of E (e, s values in global memory) standardised by its wave into z (sp values): the one
+// copy of the Pearson arithmetic, run by corr_standardise_kernel for every row and by
+// corr_bicor_kernel for a row whose MAD is zero.
+__device__ __forceinline__ void corr_pearson_row(const double* __restrict__ e, int64_t s,
+                                                 double* __restrict__ z, int64_t sp, int64_t r,
+                                                 int lane, unsigned* __restrict__ bad) {
   double sum = 0.0, lo = e[0], hi = e[0];
   for (int64_t k = lane; k < s; k += 64) {
     const double x = e[k];
@@ -82,6 +81,223 @@ __global__ __launch_bounds__(256) void corr_standardise_kernel(const double* __r
   if (!ok && lane == 0) atomicMin(bad, (unsigned)r);
   const double norm = sqrt(ss);
   for (int64_t k = lane; k < sp; k += 64) z[k] = (ok && k < s) ? (e[k] - mean) / norm : 0.0;
+}
+
+__global__ __launch_bounds__(256) void corr_standardise_kernel(const double* __restrict__ E,
+                                                               int64_t n, int64_t s,
+                                                               double* __restrict__ Z, int64_t sp,
+                                                               int64_t npad,
+                                                               unsigned* __restrict__ bad) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= npad) return;  // (wave-uniform)
+  double* z = Z + r * sp;
+  if (r >= n) {
+    for (int64_t k = lane; k < sp; k += 64) z[k] = 0.0;
+    return;
+  }
+  corr_pearson_row(E + r * s, s, z, sp, r, lane, bad);
+}
+
+// ---- the row passes of the other correlation methods ----------------------------------------
+// Both rest on one counting pass: for a value x of the row, less = #{j : v_j < x} and equal =
+// #{j : v_j == x} over the row's values v (integers, so nothing rounds; IEEE ==, so -0.0 and
+// +0.0 tie).  x then has the 1-based average rank less + (equal + 1) / 2, and it is the k-th
+// order statistic (0-based) exactly when less <= k < less + equal.  A lane counts for
+// CORR_ROW_CB of its elements (lane, lane + 64, ...) at a time while all lanes walk j together:
+// every lane reads the same v_j, a broadcast read of the row, which the wave keeps in LDS when
+// s <= CORR_ROW_LDS (four waves x 16 KiB: the 64 KiB a launch gets without opting in) and reads
+// from global memory (the caches) beyond that.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+// corr_rank_kernel 52 VGPRs, corr_bicor_kernel 60 VGPRs, scratch 0, dynamic LDS only.
+#define CORR_ROW_LDS 2048
+#define CORR_ROW_CB 4
+
+// DEV: v_j = |row[j] - med| (the deviations whose median is the MAD) instead of row[j].  A slot
+// x[c] beyond the row holds NaN and counts nothing.
+template <bool DEV>
+__device__ __forceinline__ void corr_row_counts(const double* row, int64_t s, double med,
+                                                const double (&x)[CORR_ROW_CB],
+                                                int (&less)[CORR_ROW_CB],
+                                                int (&equal)[CORR_ROW_CB]) {
+#pragma unroll
+  for (int c = 0; c < CORR_ROW_CB; ++c) less[c] = equal[c] = 0;
+#pragma unroll 4
+  for (int64_t j = 0; j < s; ++j) {
+    const double v = DEV ? fabs(row[j] - med) : row[j];
+#pragma unroll
+    for (int c = 0; c < CORR_ROW_CB; ++c) {
+      less[c] += v < x[c] ? 1 : 0;
+      equal[c] += v == x[c] ? 1 : 0;
+    }
+  }
+}
+
+// this lane's elements i0 + lane + 64 c of the row (DEV: their deviations), NaN beyond s
+template <bool DEV>
+__device__ __forceinline__ void corr_row_own(const double* row, int64_t s, double med, int64_t i0,
+                                             int lane, double (&x)[CORR_ROW_CB]) {
+#pragma unroll
+  for (int c = 0; c < CORR_ROW_CB; ++c) {
+    const int64_t i = i0 + lane + 64 * c;
+    x[c] = i < s ? (DEV ? fabs(row[i] - med) : row[i]) : __builtin_nan("");
+  }
+}
+
+// np.median of the row's finite values (DEV: of their deviations from med): the middle order
+// statistic, or (a + b) / 2 of the two middle ones.  Every element that is the k-th order
+// statistic carries the same value, so a wave maximum over -inf elsewhere broadcasts it.
+template <bool DEV>
+__device__ __forceinline__ double corr_row_median(const double* row, int64_t s, double med,
+                                                  int lane) {
+  const int64_t k0 = (s - 1) / 2, k1 = s / 2;
+  double a = -__builtin_inf(), b = -__builtin_inf();
+  for (int64_t i0 = 0; i0 < s; i0 += 64 * CORR_ROW_CB) {  // (wave-uniform trip count)
+    double x[CORR_ROW_CB];
+    int less[CORR_ROW_CB], equal[CORR_ROW_CB];
+    corr_row_own<DEV>(row, s, med, i0, lane, x);
+    corr_row_counts<DEV>(row, s, med, x, less, equal);
+#pragma unroll
+    for (int c = 0; c < CORR_ROW_CB; ++c) {
+      if (less[c] <= k0 && k0 < (int64_t)less[c] + equal[c]) a = x[c];
+      if (less[c] <= k1 && k1 < (int64_t)less[c] + equal[c]) b = x[c];
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    a = fmax(a, __shfl_xor(a, m, 64));
+    b = fmax(b, __shfl_xor(b, m, 64));
+  }
+  return k0 == k1 ? a : (a + b) / 2.0;
+}
+
+// the average ranks of a row of finite values into out (s values)
+__device__ __forceinline__ void corr_rank_row(const double* row, int64_t s, int lane,
+                                              double* __restrict__ out) {
+  for (int64_t i0 = 0; i0 < s; i0 += 64 * CORR_ROW_CB) {
+    double x[CORR_ROW_CB];
+    int less[CORR_ROW_CB], equal[CORR_ROW_CB];
+    corr_row_own<false>(row, s, 0.0, i0, lane, x);
+    corr_row_counts<false>(row, s, 0.0, x, less, equal);
+#pragma unroll
+    for (int c = 0; c < CORR_ROW_CB; ++c) {
+      const int64_t i = i0 + lane + 64 * c;
+      if (i < s) out[i] = (double)less[c] + 0.5 * (double)(equal[c] + 1);
+    }
+  }
+}
+
+// R (n x s) = the average ranks of the rows of E, one wave per row (dynamic LDS: 4 s doubles when
+// staged, none otherwise).  A row that holds a non-finite value gets NaN in every place: a
+// comparison with NaN is false, its ranks would be made of finite numbers, and
+// corr_standardise_kernel, which takes R next, must refuse the row as it refuses it in E.
+__global__ __launch_bounds__(256) void corr_rank_kernel(const double* __restrict__ E, int64_t n,
+                                                        int64_t s, double* __restrict__ R,
+                                                        int staged) {
+  extern __shared__ __attribute__((aligned(16))) double corr_rows[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  const bool live = r < n;  // (wave-uniform)
+  const double* e = E + (live ? r : 0) * s;
+  double* row = corr_rows + (staged ? (int64_t)wave * s : 0);
+  int fin = 1;
+  if (live)
+    for (int64_t k = lane; k < s; k += 64) {
+      const double x = e[k];
+      fin &= isfinite(x) ? 1 : 0;
+      if (staged) row[k] = x;
+    }
+  __syncthreads();  // the staged row is visible to every lane of its wave
+  if (!live) return;
+  double* out = R + r * s;
+  if (!__all(fin)) {
+    for (int64_t k = lane; k < s; k += 64) out[k] = __builtin_nan("");
+    return;
+  }
+  if (staged)
+    corr_rank_row(row, s, lane, out);
+  else
+    corr_rank_row(e, s, lane, out);
+}
+
+// a = (x - med) w, w = (1 - u^2)^2 where |u| < 1, else 0, u = (x - med) / d, d = 9 MAD
+__device__ __forceinline__ double corr_bicor_weighted(double x, double med, double d) {
+  const double c = x - med, u = c / d, v = 1.0 - u * u;
+  return fabs(u) < 1.0 ? c * (v * v) : 0.0;
+}
+
+// row: the row's values, in LDS or e itself; e: the row in global memory
+__device__ __forceinline__ void corr_bicor_row(const double* row, const double* __restrict__ e,
+                                               int64_t s, double* __restrict__ z, int64_t sp,
+                                               int64_t r, int lane, unsigned* __restrict__ flag) {
+  const double med = corr_row_median<false>(row, s, 0.0, lane);
+  const double mad = corr_row_median<true>(row, s, med, lane);  // (>= +0: wave-uniform)
+  if (mad == 0.0) {
+    // at least half of the row sits on its median: no robust scale.  The Pearson row instead.
+    if (lane == 0) {
+      atomicAdd(flag + 1, 1u);
+      atomicMin(flag + 2, (unsigned)r);
+    }
+    corr_pearson_row(e, s, z, sp, r, lane, flag);
+    return;
+  }
+  const double d = 9.0 * mad;
+  double ss = 0.0;
+  for (int64_t k = lane; k < s; k += 64) {
+    const double a = corr_bicor_weighted(row[k], med, d);
+    ss += a * a;
+  }
+  ss = wave_sum_f64(ss);
+  // (the upper middle deviation is > 0 and <= 2 MAD: |u| <= 2/9 and a != 0 there, so ss > 0
+  // unless a^2 underflows or overflows)
+  const bool ok = isfinite(ss) && ss > 0.0;
+  if (!ok && lane == 0) atomicMin(flag, (unsigned)r);
+  const double norm = sqrt(ss);
+  for (int64_t k = lane; k < sp; k += 64)
+    z[k] = (ok && k < s) ? corr_bicor_weighted(row[k], med, d) / norm : 0.0;
+}
+
+// Z as corr_standardise_kernel lays it out, rows standardised for the biweight midcorrelation.
+// flag[0]: the smallest bad row (atomicMin, as *bad above: a non-finite value or a constant row);
+// flag[1]: the rows that took the Pearson fallback (MAD = 0), flag[2]: the smallest of them.
+__global__ __launch_bounds__(256) void corr_bicor_kernel(const double* __restrict__ E, int64_t n,
+                                                         int64_t s, double* __restrict__ Z,
+                                                         int64_t sp, int64_t npad,
+                                                         unsigned* __restrict__ flag, int staged) {
+  extern __shared__ __attribute__((aligned(16))) double corr_rows[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  const bool live = r < n;  // (wave-uniform)
+  const double* e = E + (live ? r : 0) * s;
+  double* row = corr_rows + (staged ? (int64_t)wave * s : 0);
+  int fin = 1;
+  double lo = e[0], hi = e[0];
+  if (live)
+    for (int64_t k = lane; k < s; k += 64) {
+      const double x = e[k];
+      fin &= isfinite(x) ? 1 : 0;
+      lo = fmin(lo, x);
+      hi = fmax(hi, x);
+      if (staged) row[k] = x;
+    }
+  __syncthreads();  // the staged row is visible to every lane of its wave
+  if (r >= npad) return;
+  double* z = Z + r * sp;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    lo = fmin(lo, __shfl_xor(lo, m, 64));
+    hi = fmax(hi, __shfl_xor(hi, m, 64));
+  }
+  const bool ok = live && __all(fin) && lo < hi;
+  if (!ok) {
+    if (live && lane == 0) atomicMin(flag, (unsigned)r);
+    for (int64_t k = lane; k < sp; k += 64) z[k] = 0.0;
+    return;
+  }
+  if (staged)
+    corr_bicor_row(row, e, s, z, sp, r, lane, flag);
+  else
+    corr_bicor_row(e, e, s, z, sp, r, lane, flag);
 }
 
 // kind: N2V2R_CORR_* (include/n2v2r.h)
@@ -156,6 +372,31 @@ extern "C" hipError_t n2v2r_launch_corr_standardise(const double* E, int64_t n, 
   const int64_t npad = (n + 63) / 64 * 64;
   hipLaunchKernelGGL(corr_standardise_kernel, dim3((unsigned)(npad / 4)), dim3(256), 0, stream, E,
                      n, s, Z, n2v2r_corr_spad(s), npad, bad);
+  return hipGetLastError();
+}
+
+// R (n x s fp64) = the average ranks of the rows of E (a row with a non-finite value: NaNs)
+extern "C" hipError_t n2v2r_launch_corr_ranks(const double* E, int64_t n, int64_t s, double* R,
+                                              hipStream_t stream) {
+  if (!E || !R || n < 1 || s < 1 || n > 0x7fffffffLL || s > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  const int staged = s <= CORR_ROW_LDS;
+  hipLaunchKernelGGL(corr_rank_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256),
+                     staged ? sizeof(double) * 4 * (size_t)s : 0, stream, E, n, s, R, staged);
+  return hipGetLastError();
+}
+
+// Z as n2v2r_launch_corr_standardise lays it out, for the biweight midcorrelation; flag: three
+// words set by the caller to {0xFFFFFFFF, 0, 0xFFFFFFFF} (corr_bicor_kernel)
+extern "C" hipError_t n2v2r_launch_corr_bicor(const double* E, int64_t n, int64_t s, double* Z,
+                                              unsigned* flag, hipStream_t stream) {
+  if (!E || !Z || !flag || n < 1 || s < 1 || n > 0x7fffffffLL || s > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  const int64_t npad = (n + 63) / 64 * 64;
+  const int staged = s <= CORR_ROW_LDS;
+  hipLaunchKernelGGL(corr_bicor_kernel, dim3((unsigned)(npad / 4)), dim3(256),
+                     staged ? sizeof(double) * 4 * (size_t)s : 0, stream, E, n, s, Z,
+                     n2v2r_corr_spad(s), npad, flag, staged);
   return hipGetLastError();
 }
 

@@ -124,6 +124,10 @@ hipError_t n2v2r_launch_syrk_f64(const double* W, int64_t sk, int64_t si, int64_
 int64_t n2v2r_corr_spad(int64_t s);
 hipError_t n2v2r_launch_corr_standardise(const double* E, int64_t n, int64_t s, double* Z,
                                          unsigned* bad, hipStream_t stream);
+hipError_t n2v2r_launch_corr_ranks(const double* E, int64_t n, int64_t s, double* R,
+                                   hipStream_t stream);
+hipError_t n2v2r_launch_corr_bicor(const double* E, int64_t n, int64_t s, double* Z,
+                                   unsigned* flag, hipStream_t stream);
 hipError_t n2v2r_launch_corr_tiles(const double* Z, int64_t s, int64_t n, int64_t row0,
                                    int64_t nloc, float* A, int64_t lda, int kind, double power,
                                    hipStream_t stream);
@@ -769,7 +773,7 @@ int multi_set_layer_csr(n2v2r_handle* h, int k, int64_t n, int64_t nnz, const in
                         const int32_t* indices, const float* data, int symmetric);
 int multi_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int symmetric);
 int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, const double* E,
-                         int kind, double power);
+                         int kind, double power, int method, int64_t* fallback);
 int multi_transform_layer(n2v2r_handle* h, int k, int flags, double threshold,
                           double top_percent_keep, n2v2r_transform_stats* stats);
 int multi_tom_layer(n2v2r_handle* h, int k, int type);

@@ -318,6 +318,51 @@ int set_layer_rows_directed(n2v2r_handle* h, int k, const int64_t* aip, const in
 }
 }  // namespace n2v2r_int
 
+namespace {
+// what the row pass of a correlation method reports (corr.hip)
+struct CorrRows {
+  unsigned bad = 0xFFFFFFFFu;     // the smallest bad row, or 0xFFFFFFFF
+  int64_t fallback[2] = {0, -1};  // bicor rows with MAD = 0 (the Pearson row): count, smallest
+};
+
+bool corr_method_known(int method) {
+  return method == N2V2R_COR_PEARSON || method == N2V2R_COR_SPEARMAN ||
+         method == N2V2R_COR_BICOR;
+}
+
+// z (npad x n2v2r_corr_spad(s)) = the rows of e (n x s, on the device) standardised for `method`:
+// Pearson by corr_standardise_kernel, Spearman by the same kernel on the rows' average ranks,
+// bicor by corr_bicor_kernel.  flag: four device words of scratch.  The stream is synchronised
+// on return (the rank buffer dies here).
+CorrRows corr_standardise_rows(hipStream_t st, const double* e, int64_t n, int64_t s, int method,
+                               double* z, unsigned* flag) {
+  CorrRows out;
+  DevBuf ranks;
+  HIPCHK(hipMemsetAsync(flag, 0xFF, sizeof(unsigned), st));
+  if (method == N2V2R_COR_BICOR) {
+    HIPCHK(hipMemsetAsync(flag + 1, 0, sizeof(unsigned), st));
+    HIPCHK(hipMemsetAsync(flag + 2, 0xFF, sizeof(unsigned), st));
+    HIPCHK(n2v2r_launch_corr_bicor(e, n, s, z, flag, st));
+  } else if (method == N2V2R_COR_SPEARMAN) {
+    ranks.ensure_raw(sizeof(double) * n * s);
+    HIPCHK(n2v2r_launch_corr_ranks(e, n, s, ranks.as<double>(), st));
+    HIPCHK(n2v2r_launch_corr_standardise(ranks.as<double>(), n, s, z, flag, st));
+  } else {
+    HIPCHK(n2v2r_launch_corr_standardise(e, n, s, z, flag, st));
+  }
+  unsigned w[3] = {0, 0, 0};
+  HIPCHK(hipMemcpyAsync(w, flag, sizeof(unsigned) * (method == N2V2R_COR_BICOR ? 3 : 1),
+                        hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  out.bad = w[0];
+  if (method == N2V2R_COR_BICOR && w[1] > 0) {
+    out.fallback[0] = (int64_t)w[1];
+    out.fallback[1] = (int64_t)w[2];
+  }
+  return out;
+}
+}  // namespace
+
 extern "C" {
 
 int n2v2r_set_num_layers(n2v2r_handle* h, int num_layers, int64_t n) {
@@ -591,9 +636,18 @@ int n2v2r_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int
 // (8 n samples bytes, on every rank of a partitioned handle), standardised on the GPU, and this
 // rank's rows of t(corrcoef(E)) are written straight into the layer's dA by the fused tile
 // kernel.  The layer counts as not loaded from the first check on until the kernels succeeded.
+// method: N2V2R_COR_*, the way the rows are standardised (corr_standardise_rows above); the tile
+// product and everything after it are the same for all of them.
 int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, const double* E,
                          int kind, double power) {
-  if (h && h->multi()) return multi_set_layer_corr(h, k, n, samples, E, kind, power);
+  return n2v2r_set_layer_corr_method(h, k, n, samples, E, kind, power, N2V2R_COR_PEARSON, nullptr);
+}
+
+int n2v2r_set_layer_corr_method(n2v2r_handle* h, int k, int64_t n, int64_t samples,
+                                const double* E, int kind, double power, int method,
+                                int64_t* fallback) {
+  if (h && h->multi())
+    return multi_set_layer_corr(h, k, n, samples, E, kind, power, method, fallback);
   return guarded(h, [&]() -> int {
     if (k < 0 || k >= h->K || n != h->n || n < 1 || !E) {
       h->set_err("bad co-expression arguments for layer %d", k);
@@ -621,6 +675,10 @@ int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, con
                  power);
       return N2V2R_ERR_BAD_ARG;
     }
+    if (!corr_method_known(method)) {
+      h->set_err("layer %d: unknown correlation method %d", k, method);
+      return N2V2R_ERR_BAD_ARG;
+    }
     for (int j = 0; j < h->K; ++j)
       if (j != k && h->layers[j]->loaded && !h->layers[j]->dense) {
         h->err = "layers must be all CSR or all dense";
@@ -635,15 +693,11 @@ int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, con
     flag.ensure_raw(sizeof(unsigned) * 4);
     HIPCHK(hipMemcpyAsync(e.p, E, sizeof(double) * n * samples, hipMemcpyHostToDevice, st));
     h->h2d_layer_bytes += 8 * n * samples;
-    HIPCHK(hipMemsetAsync(flag.p, 0xFF, sizeof(unsigned), st));
-    HIPCHK(n2v2r_launch_corr_standardise(e.as<double>(), n, samples, z.as<double>(),
-                                         flag.as<unsigned>(), st));
-    unsigned bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad != 0xFFFFFFFFu) {
+    const CorrRows rows = corr_standardise_rows(st, e.as<double>(), n, samples, method,
+                                                z.as<double>(), flag.as<unsigned>());
+    if (rows.bad != 0xFFFFFFFFu) {
       h->set_err("layer %d: row %u of the expression matrix holds a non-finite value or is "
-                 "constant (zero variance): its correlations are undefined", k, bad);
+                 "constant (zero variance): its correlations are undefined", k, rows.bad);
       return N2V2R_ERR_BAD_ARG;
     }
     L.dense = true;
@@ -656,6 +710,7 @@ int n2v2r_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, con
     HIPCHK(hipStreamSynchronize(st));  // e and z die here
     L.symmetric = true;
     L.loaded = true;
+    if (fallback) std::copy(rows.fallback, rows.fallback + 2, fallback);
     return N2V2R_OK;
   });
 }
@@ -1400,7 +1455,8 @@ int n2v2r_project(n2v2r_handle* h, int64_t m, int64_t n, const double* W, int on
 // chunks: 0 = n2v2r_soft_chunks(n); ms (optional): the scan kernel's time from one event pair.
 static int soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
                              int kind, const double* powers, int n_powers, int chunks,
-                             double* conn, int* chunks_used, double* ms) {
+                             double* conn, int* chunks_used, double* ms,
+                             int method = N2V2R_COR_PEARSON, int64_t* fallback = nullptr) {
   if (h && h->multi()) h = h->ranks[0];  // no collective: rank 0's GPU
   return guarded(h, [&]() -> int {
     if (!E || !powers || !conn || n < 1 || n > 0x7fffffffLL) {
@@ -1432,6 +1488,10 @@ static int soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const 
       h->set_err("soft_connectivity: unknown correlation kind %d", kind);
       return N2V2R_ERR_BAD_ARG;
     }
+    if (!corr_method_known(method)) {
+      h->set_err("soft_connectivity: unknown correlation method %d", method);
+      return N2V2R_ERR_BAD_ARG;
+    }
     const int64_t nt = (n + 63) / 64, npad = nt * 64, sp = n2v2r_corr_spad(samples);
     if (chunks < 0 || chunks > nt || chunks > 65535) {
       h->set_err("soft_connectivity: chunks must lie in [0, %lld], got %d", (long long)nt, chunks);
@@ -1448,15 +1508,11 @@ static int soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const 
     out.ensure_raw(sizeof(double) * n_powers * n);
     HIPCHK(hipMemcpyAsync(e.p, E, sizeof(double) * n * samples, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(pw.p, powers, sizeof(double) * n_powers, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(flag.p, 0xFF, sizeof(unsigned), st));
-    HIPCHK(n2v2r_launch_corr_standardise(e.as<double>(), n, samples, z.as<double>(),
-                                         flag.as<unsigned>(), st));
-    unsigned bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad != 0xFFFFFFFFu) {
+    const CorrRows rows = corr_standardise_rows(st, e.as<double>(), n, samples, method,
+                                                z.as<double>(), flag.as<unsigned>());
+    if (rows.bad != 0xFFFFFFFFu) {
       h->set_err("soft_connectivity: row %u of the expression matrix holds a non-finite value or "
-                 "is constant (zero variance): its correlations are undefined", bad);
+                 "is constant (zero variance): its correlations are undefined", rows.bad);
       return N2V2R_ERR_BAD_ARG;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1488,6 +1544,7 @@ static int soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const 
     if (err != hipSuccess) throw HipFail{err, "soft_connectivity"};
     if (ms) *ms = (double)t;
     if (chunks_used) *chunks_used = G;
+    if (fallback) std::copy(rows.fallback, rows.fallback + 2, fallback);
     return N2V2R_OK;
   });
 }
@@ -1495,6 +1552,119 @@ static int soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const 
 int n2v2r_soft_connectivity(n2v2r_handle* h, int64_t n, int64_t samples, const double* E, int kind,
                             const double* powers, int n_powers, double* conn) {
   return soft_connectivity(h, n, samples, E, kind, powers, n_powers, 0, conn, nullptr, nullptr);
+}
+
+int n2v2r_soft_connectivity_method(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                                   int kind, const double* powers, int n_powers, int method,
+                                   double* conn, int64_t* fallback) {
+  return soft_connectivity(h, n, samples, E, kind, powers, n_powers, 0, conn, nullptr, nullptr,
+                           method, fallback);
+}
+
+// diagnostics (n2v2r_diag.h): the row passes of the correlation methods apart from the tile
+// product.  Buffers local to the call, rank 0's GPU on a multi handle (no collective).
+int n2v2r_corr_ranks(n2v2r_handle* h, int64_t n, int64_t samples, const double* E, double* R) {
+  if (h && h->multi()) h = h->ranks[0];
+  return guarded(h, [&]() -> int {
+    if (!E || !R || n < 1 || n > 0x7fffffffLL || samples < 2 || samples > 0x7fffffffLL) {
+      h->set_err("corr_ranks: E and R must be given, 1 <= n < 2^31 and 2 <= samples < 2^31");
+      return N2V2R_ERR_BAD_ARG;
+    }
+    hipStream_t st = h->stream;
+    DevBuf e, r;
+    e.ensure_raw(sizeof(double) * n * samples);
+    r.ensure_raw(sizeof(double) * n * samples);
+    HIPCHK(hipMemcpyAsync(e.p, E, sizeof(double) * n * samples, hipMemcpyHostToDevice, st));
+    HIPCHK(n2v2r_launch_corr_ranks(e.as<double>(), n, samples, r.as<double>(), st));
+    HIPCHK(hipMemcpyAsync(R, r.p, sizeof(double) * n * samples, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // e and r die here
+    return N2V2R_OK;
+  });
+}
+
+int n2v2r_corr_standardise(n2v2r_handle* h, int64_t n, int64_t samples, const double* E,
+                           int method, double* Z, int64_t* bad_row) {
+  if (h && h->multi()) h = h->ranks[0];
+  return guarded(h, [&]() -> int {
+    if (!E || !Z || n < 1 || n > 0x7fffffffLL || samples < 2 || samples > 0x7fffffffLL) {
+      h->set_err("corr_standardise: E and Z must be given, 1 <= n < 2^31 and 2 <= samples < "
+                 "2^31");
+      return N2V2R_ERR_BAD_ARG;
+    }
+    if (!corr_method_known(method)) {
+      h->set_err("corr_standardise: unknown correlation method %d", method);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    hipStream_t st = h->stream;
+    const int64_t npad = (n + 63) / 64 * 64, sp = n2v2r_corr_spad(samples);
+    DevBuf e, z, flag;
+    e.ensure_raw(sizeof(double) * n * samples);
+    z.ensure_raw(sizeof(double) * npad * sp);
+    flag.ensure_raw(sizeof(unsigned) * 4);
+    HIPCHK(hipMemcpyAsync(e.p, E, sizeof(double) * n * samples, hipMemcpyHostToDevice, st));
+    const CorrRows rows = corr_standardise_rows(st, e.as<double>(), n, samples, method,
+                                                z.as<double>(), flag.as<unsigned>());
+    HIPCHK(hipMemcpy2DAsync(Z, sizeof(double) * samples, z.p, sizeof(double) * sp,
+                            sizeof(double) * samples, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // e and z die here
+    if (bad_row) *bad_row = rows.bad == 0xFFFFFFFFu ? -1 : (int64_t)rows.bad;
+    return N2V2R_OK;
+  });
+}
+
+// the row kernel of a method alone, timed with HIP events (the flag words are not reset between
+// the launches: their atomics run as in a build, their values are not read)
+int n2v2r_bench_corr_rows(n2v2r_handle* h, int64_t n, int64_t samples, const double* E, int method,
+                          int reps, double* ms) {
+  if (h && h->multi()) h = h->ranks[0];
+  return guarded(h, [&]() -> int {
+    if (!E || !ms || reps < 1 || n < 1 || n > 0x7fffffffLL || samples < 2 ||
+        samples > 0x7fffffffLL || !corr_method_known(method)) {
+      h->err = "bench_corr_rows: E and ms, reps >= 1, 1 <= n < 2^31, 2 <= samples < 2^31 and a "
+               "known method";
+      return N2V2R_ERR_BAD_ARG;
+    }
+    hipStream_t st = h->stream;
+    const int64_t npad = (n + 63) / 64 * 64, sp = n2v2r_corr_spad(samples);
+    const bool ranks = method == N2V2R_COR_SPEARMAN;
+    DevBuf e, o, flag;
+    e.ensure_raw(sizeof(double) * n * samples);
+    o.ensure_raw(sizeof(double) * (ranks ? n * samples : npad * sp));
+    flag.ensure_raw(sizeof(unsigned) * 4);
+    HIPCHK(hipMemcpyAsync(e.p, E, sizeof(double) * n * samples, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(flag.p, 0xFF, sizeof(unsigned) * 4, st));
+    auto launch = [&]() {
+      if (ranks) return n2v2r_launch_corr_ranks(e.as<double>(), n, samples, o.as<double>(), st);
+      if (method == N2V2R_COR_BICOR)
+        return n2v2r_launch_corr_bicor(e.as<double>(), n, samples, o.as<double>(),
+                                       flag.as<unsigned>(), st);
+      return n2v2r_launch_corr_standardise(e.as<double>(), n, samples, o.as<double>(),
+                                           flag.as<unsigned>(), st);
+    };
+    HIPCHK(launch());  // warm-up
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    const hipError_t ce = hipEventCreate(&e1);
+    if (ce != hipSuccess) {
+      (void)hipEventDestroy(e0);
+      throw HipFail{ce, "hipEventCreate"};
+    }
+    hipError_t err = hipSuccess;
+    for (int r = 0; r < reps && err == hipSuccess; ++r) {
+      err = hipEventRecord(e0, st);
+      if (err == hipSuccess) err = launch();
+      if (err == hipSuccess) err = hipEventRecord(e1, st);
+      if (err == hipSuccess) err = hipEventSynchronize(e1);
+      float t = 0.f;
+      if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+      ms[r] = (double)t;
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // the local buffers die here
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (err != hipSuccess) throw HipFail{err, "bench_corr_rows"};
+    return N2V2R_OK;
+  });
 }
 
 // diagnostics (n2v2r_diag.h): the scan with the chunk count given, the scan kernel timed

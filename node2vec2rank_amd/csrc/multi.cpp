@@ -239,12 +239,16 @@ int multi_set_layer_dense(n2v2r_handle* h, int k, int64_t n, const float* A, int
   return fanout(h, [&](n2v2r_handle* r, int) { return n2v2r_set_layer_dense(r, k, n, A, symmetric); });
 }
 
-// every rank uploads the (small) expression matrix whole and builds its own row band
+// every rank uploads the (small) expression matrix whole and builds its own row band; every rank
+// standardises all of E and counts the same MAD fallbacks: rank 0's are returned
 int multi_set_layer_corr(n2v2r_handle* h, int k, int64_t n, int64_t samples, const double* E,
-                         int kind, double power) {
-  return fanout(h, [&](n2v2r_handle* r, int) {
-    return n2v2r_set_layer_corr(r, k, n, samples, E, kind, power);
+                         int kind, double power, int method, int64_t* fallback) {
+  std::vector<int64_t> fb(2 * h->ranks.size(), 0);
+  const int st = fanout(h, [&](n2v2r_handle* r, int i) {
+    return n2v2r_set_layer_corr_method(r, k, n, samples, E, kind, power, method, &fb[2 * i]);
   });
+  if (st == N2V2R_OK && fallback) std::copy(fb.begin(), fb.begin() + 2, fallback);
+  return st;
 }
 
 // collective inside: every rank selects over the summed histograms and returns the global stats

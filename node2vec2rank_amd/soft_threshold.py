@@ -17,7 +17,7 @@ import math
 
 import numpy as np
 
-from .coexpression import Coexpression
+from .coexpression import Coexpression, method_name
 
 # WGCNA's default powerVector, c(1:10, seq(12, 20, 2))
 DEFAULT_POWERS = tuple(float(p) for p in (*range(1, 11), *range(12, 21, 2)))
@@ -105,10 +105,12 @@ def power_estimate(table, r2_cut: float = 0.85):
 class SoftThreshold:
     """What ``pick_soft_threshold`` returns: ``.connectivity`` (P x n float64, row q the
     connectivities at ``.powers[q]``), ``.table`` (``fit_table``'s DataFrame) and
-    ``.power_estimate`` (``power_estimate`` of the table: a float or ``None``)."""
+    ``.power_estimate`` (``power_estimate`` of the table: a float or ``None``); ``.kind`` and
+    ``.method`` are those of the network scanned."""
 
-    def __init__(self, kind, powers, connectivity, table, estimate, r2_cut):
+    def __init__(self, kind, powers, connectivity, table, estimate, r2_cut, method="pearson"):
         self.kind = kind
+        self.method = method
         self.powers = powers
         self.connectivity = connectivity
         self.table = table
@@ -116,15 +118,16 @@ class SoftThreshold:
         self.r2_cut = r2_cut
 
     def __repr__(self):
-        return (f"SoftThreshold(kind={self.kind!r}, powers={len(self.powers)}, "
+        method = "" if self.method == "pearson" else f"method={self.method!r}, "
+        return (f"SoftThreshold(kind={self.kind!r}, {method}powers={len(self.powers)}, "
                 f"n={self.connectivity.shape[1]}, power_estimate={self.power_estimate!r})")
 
 
-def _validate(expression, kind, powers, r2_cut, n_breaks):
+def _validate(expression, kind, powers, r2_cut, n_breaks, method="pearson"):
     if isinstance(expression, Coexpression):
-        layer = expression  # (its own kind is the one scanned)
+        layer = expression  # (its own kind and method are the ones scanned)
     else:
-        layer = Coexpression(expression, kind=kind)
+        layer = Coexpression(expression, kind=kind, method=method_name(method))
     if layer.kind not in SCAN_KINDS:
         raise ValueError(f"a {layer.kind!r} layer takes no power (r may be negative): the kinds "
                          f"to scan are {list(SCAN_KINDS)}")
@@ -151,26 +154,34 @@ def _validate(expression, kind, powers, r2_cut, n_breaks):
 
 
 def pick_soft_threshold(expression, kind: str = "unsigned", powers=None, r2_cut: float = 0.85,
-                        n_breaks: int = 10, engine=None) -> SoftThreshold:
+                        n_breaks: int = 10, engine=None, method: str = "pearson") -> SoftThreshold:
     """WGCNA's ``pickSoftThreshold`` for the rows of ``expression``.
 
     expression: ``n x samples`` (an array or a DataFrame, as ``Coexpression`` takes it), or a
-        ``Coexpression``, whose own ``kind`` is used (its power and options play no part).
+        ``Coexpression``, whose own ``kind`` and ``method`` are used (its power and options play
+        no part).
     kind: ``"unsigned"``, ``"signed"`` or ``"signed hybrid"``.
     powers: up to 32 candidate exponents, each >= 1; default WGCNA's ``c(1:10, seq(12, 20, 2))``.
     r2_cut: the signed scale-free fit a power must exceed to be the estimate.
     n_breaks: bins of the connectivity histogram (``scaleFreeFitIndex``'s ``nBreaks``).
     engine: the ``Engine`` to run on (default: the process-wide engine of device 0); its loaded
         layers and embedding are left alone.
+    method: ``"pearson"``, ``"spearman"`` or ``"bicor"``, as ``Coexpression`` takes it.  A bicor
+        scan in which rows have zero MAD warns (``RuntimeWarning``) as ``Engine.set_layers`` does.
 
     Every violation of the above is a ``ValueError`` before any GPU work; rows the correlation is
     undefined for (constant, non-finite) are a ``ValueError`` from the engine, by row index.
 
     The formulas are WGCNA's, restated (see the module docstring): parity is by formula."""
-    layer, pw, cut, nb = _validate(expression, kind, powers, r2_cut, n_breaks)
+    layer, pw, cut, nb = _validate(expression, kind, powers, r2_cut, n_breaks, method)
     if engine is None:
         from ._lib import default_engine
         engine = default_engine()
-    conn = engine.soft_connectivity(layer.expression, kind=layer.kind, powers=pw)
+    if layer.method == "pearson":  # (an engine that knows no method keyword still serves)
+        conn = engine.soft_connectivity(layer.expression, kind=layer.kind, powers=pw)
+    else:
+        conn = engine.soft_connectivity(layer.expression, kind=layer.kind, powers=pw,
+                                        method=layer.method)
     table = fit_table(pw, conn, nb)
-    return SoftThreshold(layer.kind, pw, conn, table, power_estimate(table, cut), cut)
+    return SoftThreshold(layer.kind, pw, conn, table, power_estimate(table, cut), cut,
+                         layer.method)
