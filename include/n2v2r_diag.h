@@ -175,6 +175,50 @@ int n2v2r_ortho_pass(n2v2r_handle* h, int b, int nq, const float* Q, float* Z, i
 int n2v2r_rr_band_top(n2v2r_handle* h, int c, int kp, const double* hband, int64_t hband_len,
                       const double* theta_prev, int p, double* w, float* S);
 
+/* What one n2v2r_rr_stage ran. */
+typedef struct n2v2r_rr_info {
+  int form_ran;       /* 0 Sturm, 1 BandReduce, 2 DenseFromBand, 3 Dense: the form whose result is
+                         returned (-1: the call was refused) */
+  int sturm_err;      /* err[0] of the Sturm launch (a vector failed its residual check); -1: Sturm
+                         did not run */
+  int second_solves;  /* err[1]: vectors that took the second solve; -1 likewise */
+  int reduce_err;     /* the reducing path's error word (the bulge chase gave up); -1: it did not
+                         run */
+  int tri_coop;       /* dense forms: 1 the multi-workgroup tridiagonalisation ran, 0 the
+                         one-workgroup kernel (N2V2R_RR_TRI=1, no room for the grid, or after a
+                         timed-out grid barrier); -1 n/a */
+  int msect_points, msect_rounds; /* Sturm: points per eigenvalue per multisection round and the
+                         rounds launched (the launcher's own rule); 0 otherwise */
+  int reserved;
+} n2v2r_rr_info;
+
+/* One Rayleigh-Ritz of a Krylov-Schur projected matrix alone, in one chosen form (tests), through
+ * the solver's launchers on buffers of its own.  c, kp, hband, hband_len, theta_prev, p, w, S: as
+ * n2v2r_rr_band_top, within the launchers' own limits: 16 <= c <= 768, c % 8 == 0, kp % 8 == 0,
+ * kp + 8 <= c, 1 <= p <= c.  form:
+ *   -1  as a fit moves: the Sturm form, and when a vector fails its check (sturm_err) the form the
+ *       solver takes next, by the solver's own rule at (kp, c): the reducing path while
+ *       kp + 8 <= 192 and c <= 640, else the dense steps on H expanded from the band
+ *       (env N2V2R_RR_STAGE_TEST_STURM_FAIL=1, tests: a good Sturm result is discarded and that
+ *       form runs; sturm_err still reports the launch's own word);
+ *    0  the Sturm form alone; its result is returned even when sturm_err != 0;
+ *    1  the reducing path alone (kp + 8 <= 192);
+ *    2  rr_band_expand_kernel into a c x c matrix, then the dense steps (tridiagonalisation,
+ *       bisection + inverse iteration, back-transform).
+ * Y (optional): c x p fp64 row-major, the eigenvectors in fp64 where the form holds them in H's
+ * basis: the Sturm form does (its inverse iteration works on H itself).  The reducing path and the
+ * dense steps hold fp64 vectors of their tridiagonal only and back-transform into fp32 S: Y comes
+ * back as NaN bytes from them.  The device buffers behind w, S and Y are filled with NaN bytes
+ * before each form runs, so a column no launch wrote shows (the first kp entries behind w hold
+ * theta_prev on entry: the launchers read and write one buffer).  info (optional): what ran.  The
+ * handle's embedding and ranking results are left alone, and a later fit is bit-identical to one
+ * without the call.  N2V2R_ERR_BAD_ARG for a shape outside the limits above or one the form's
+ * launcher refuses, a short hband_len, a NULL hband, w or S (theta_prev with kp > 0), and a form
+ * outside -1 .. 2. */
+int n2v2r_rr_stage(n2v2r_handle* h, int c, int kp, const double* hband, int64_t hband_len,
+                   const double* theta_prev, int p, int form, double* w, float* S,
+                   double* Y /* optional, c x p */, n2v2r_rr_info* info);
+
 /* Layer bytes each rank copied host -> device so far (one-GPU handle: one entry): row pointers,
  * column indices and values of every CSR layer ingest and the 8 n samples bytes of every
  * n2v2r_set_layer_corr (each rank uploads E whole), into per_rank[0 .. min(W, cap)).  Returns the

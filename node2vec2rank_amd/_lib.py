@@ -59,7 +59,7 @@ EXPORTED = [
     "n2v2r_block_gram", "n2v2r_ortho_pass", "n2v2r_soft_connectivity",
     "n2v2r_soft_connectivity_chunks", "n2v2r_set_layer_corr_method",
     "n2v2r_soft_connectivity_method", "n2v2r_corr_ranks", "n2v2r_corr_standardise",
-    "n2v2r_bench_corr_rows",
+    "n2v2r_bench_corr_rows", "n2v2r_rr_stage",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -112,6 +112,15 @@ class PassInfo(ctypes.Structure):
                 ("stage", ctypes.c_int), ("nwg", ctypes.c_int), ("apply_kernel", ctypes.c_int),
                 ("reserved", ctypes.c_int), ("fill_seed", ctypes.c_uint64)]
 
+
+class RrInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("form_ran", "sturm_err", "second_solves",
+                                            "reduce_err", "tri_coop", "msect_points",
+                                            "msect_rounds", "reserved")]
+
+
+# n2v2r_rr_stage's form / n2v2r_rr_info.form_ran
+RR_AS_FIT, RR_STURM, RR_BAND_REDUCE, RR_DENSE_FROM_BAND, RR_DENSE = -1, 0, 1, 2, 3
 
 # n2v2r_pass_info.gram_form
 GRAM_STREAM, GRAM_LINES, GRAM_NARROW, GRAM_MFMA = 0, 1, 2, 3
@@ -207,6 +216,8 @@ def load(path: str | None = None):
                                       _vp, _vp, _vp, _vp, ctypes.POINTER(PassInfo)]),
             "n2v2r_rr_band_top": (_i, [_vp, _i, _i, _p(np.float64), ctypes.c_int64, _vp, _i,
                                        _p(np.float64), _p(np.float32)]),
+            "n2v2r_rr_stage": (_i, [_vp, _i, _i, _vp, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp,
+                                    ctypes.POINTER(RrInfo)]),
             "n2v2r_set_layer_dense": (_i, [_vp, _i, _i64, _p(np.float32), _i]),
             "n2v2r_project": (_i, [_vp, _i64, _i64, _p(np.float64), _i, _p(np.float64)]),
             "n2v2r_comm_unique_id": (_i, [ctypes.c_char_p, ctypes.c_size_t]),
@@ -1085,6 +1096,23 @@ class Engine:
             None if tp is None else tp.ctypes.data_as(ctypes.c_void_p), int(p), w, S),
             "rr_band_top")
         return w, S
+
+    def rr_stage(self, hband, c: int, kp: int, theta_prev, p: int, form: int = RR_AS_FIT):
+        """One Rayleigh-Ritz of a Krylov-Schur projected matrix in one chosen form (see
+        n2v2r_rr_stage; form: RR_AS_FIT, RR_STURM, RR_BAND_REDUCE or RR_DENSE_FROM_BAND).
+        Returns (w, S, Y, info): p fp64 values, (c, p) fp32 and fp64 vectors (Y is NaN from the
+        forms that hold no fp64 vectors in H's basis) and a dict of n2v2r_rr_info's fields."""
+        hband = np.ascontiguousarray(hband, dtype=np.float64).ravel()
+        tp = None if theta_prev is None else np.ascontiguousarray(theta_prev, dtype=np.float64)
+        w = np.empty(max(int(p), 0), dtype=np.float64)
+        S = np.empty((max(int(c), 0), w.size), dtype=np.float32)
+        Y = np.empty(S.shape, dtype=np.float64)
+        info = RrInfo()
+        vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self.lib.n2v2r_rr_stage(
+            self.h, int(c), int(kp), vp(hband), int(hband.size), vp(tp), int(p), int(form),
+            vp(w), vp(S), vp(Y), ctypes.byref(info)), "rr_stage")
+        return w, S, Y, {k: getattr(info, k) for k, _ in RrInfo._fields_}
 
     def synchronize(self):
         self._check(self.lib.n2v2r_synchronize(self.h), "synchronize")

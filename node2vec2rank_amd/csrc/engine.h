@@ -167,7 +167,7 @@ hipError_t n2v2r_launch_transpose(const float* in, int64_t ldi, int64_t rows, in
 hipError_t n2v2r_launch_mismatch(const float* a, const float* b, int64_t ld, int64_t rows,
                                  int64_t cols, unsigned long long* count, hipStream_t stream);
 hipError_t n2v2r_launch_rr_tridiag(double* A, int c, double* d, double* e, double* tau, double* V,
-                                   void* scratch, hipStream_t stream);
+                                   void* scratch, hipStream_t stream, int* coop_ran = nullptr);
 size_t n2v2r_rr_tridiag_scratch_bytes(int c);
 int* n2v2r_rr_tridiag_err(void* scratch, int c);
 hipError_t n2v2r_launch_rr_tri_eig(const double* d, const double* e, int c, int p, double* w,
@@ -187,6 +187,7 @@ hipError_t n2v2r_launch_rr_sturm(const double* hband, int c, int kp, double* the
                                  size_t scr_elems, double* Y, float* S, int ldS, int p, int* err,
                                  hipStream_t stream);
 size_t n2v2r_rr_sturm_scratch(int c, int p);
+void n2v2r_rr_sturm_msect(int p, int* points, int* rounds);
 hipError_t n2v2r_launch_rr_band_expand(const double* hband, int c, int kp, const double* theta,
                                        double* H, hipStream_t stream);
 hipError_t n2v2r_launch_csr_scan(const int64_t* ip, const int32_t* ix, const float* dv,
@@ -209,6 +210,28 @@ hipError_t n2v2r_launch_csr_rebase(const int64_t* ip, int64_t r0, int64_t nr, in
 inline bool rr_sturm_enabled() {
   const char* e = std::getenv("N2V2R_RR");
   return !(e && e[0] == 'b');
+}
+
+// The form a cycle's Rayleigh-Ritz takes.  A cycle starts with Sturm, BandReduce (N2V2R_RR=b)
+// or Dense (no band kept) and moves only towards Dense: a failed Sturm result goes to
+// BandReduce, or past the reducing path's arrow to DenseFromBand; a failed BandReduce to Dense.
+// (The values are n2v2r_rr_info.form_ran's.)
+enum class RrForm {
+  Sturm = 0,          // banded: bisection + band inverse iteration on the saved band columns
+  BandReduce = 1,     // banded: arrow reduction + bulge chase to a tridiagonal
+  DenseFromBand = 2,  // dense steps on H expanded from the band columns
+  Dense = 3           // dense steps on H = Q^T W
+};
+inline bool banded(RrForm f) { return f == RrForm::Sturm || f == RrForm::BandReduce; }
+
+// The reducing path takes kp kept Ritz vectors in a basis of c columns: its arrow (kp + 8 rows)
+// is LDS-resident up to 192 rows, its chase measured up to 640 columns.
+constexpr int kReduceMaxc = 640;
+inline bool rr_reduce_fits(int kp, int c) { return kp + 8 <= 192 && c <= kReduceMaxc; }
+// The form that follows a failed Sturm result at (kp, c): a fit asks at its largest shape
+// (keep, c_max), as its buffers are sized; n2v2r_rr_stage at the shape of the call.
+inline RrForm rr_after_sturm(int kp, int c) {
+  return rr_reduce_fits(kp, c) ? RrForm::BandReduce : RrForm::DenseFromBand;
 }
 
 // Lean images (banded Sturm Rayleigh-Ritz, one GPU) unless N2V2R_LEAN_W=0.  Read per fit.

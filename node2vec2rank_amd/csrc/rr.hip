@@ -1050,7 +1050,8 @@ extern "C" hipError_t n2v2r_launch_rr_tri_inviter(const double* d, const double*
 // scratch (device, >= n2v2r_rr_tridiag_scratch_bytes(c)): the multi-workgroup form
 // (rr_tridiag_coop_kernel); NULL: the one-workgroup kernel (handles whose ranks share one device
 // pass NULL: their concurrent launches could not all be resident).  N2V2R_RR_TRI=1
-// forces the one-workgroup kernel.
+// forces the one-workgroup kernel.  coop_ran (optional): 1 when the multi-workgroup kernel was
+// launched, 0 for the one-workgroup kernel.
 static hipError_t launch_rr_tridiag_coop(double* A, int c, double* d, double* e, double* tau,
                                          double* V, void* scratch, hipStream_t stream) {
   const int nt = (c + TRC_TS - 1) / TRC_TS;
@@ -1109,13 +1110,18 @@ extern "C" int* n2v2r_rr_tridiag_err(void* scratch, int c) {
 }
 
 extern "C" hipError_t n2v2r_launch_rr_tridiag(double* A, int c, double* d, double* e, double* tau,
-                                              double* V, void* scratch, hipStream_t stream) {
+                                              double* V, void* scratch, hipStream_t stream,
+                                              int* coop_ran) {
   if (c < 3 || c > RR_MAXC) return hipErrorInvalidValue;
+  if (coop_ran) *coop_ran = 0;
   const char* ev = std::getenv("N2V2R_RR_TRI");  // read per call (tests switch it)
   const bool force_one = ev && std::atoi(ev) == 1;
   if (scratch && !force_one) {
     const hipError_t er = launch_rr_tridiag_coop(A, c, d, e, tau, V, scratch, stream);
-    if (er != hipErrorInvalidValue) return er;
+    if (er != hipErrorInvalidValue) {
+      if (coop_ran) *coop_ran = 1;
+      return er;
+    }
   }
   // 1024 threads up to c = 512; 512 threads (twice the registers per lane) beyond.  Even c
   // (every UASE basis: c = blocks x b): 16-B column-pair accesses.

@@ -751,6 +751,21 @@ static int rs_msect_m(int p, int nt = RS_MS_THREADS) {
   return nt * m;
 }
 
+// rounds until the bracket is below 1e-10 ||H|| (3 at p = 80, M = 768; 4 at p = 160, M = 256)
+static int rs_msect_rounds(int pm, int M) {
+  int rounds = 1;
+  for (double wdt = 2.0 / ((double)pm * M + 1.0); wdt > 1e-10; wdt /= (double)(M + 1)) ++rounds;
+  return rounds;
+}
+
+// the multisection n2v2r_launch_rr_sturm runs for p wanted eigenvalues: points per eigenvalue
+// per round and rounds launched (diagnostics)
+extern "C" void n2v2r_rr_sturm_msect(int p, int* points, int* rounds) {
+  const int M = rs_msect_m(p, rs_msect_threads());
+  *points = M;
+  *rounds = rs_msect_rounds(p, M);
+}
+
 extern "C" size_t n2v2r_rr_sturm_scratch(int c, int p) {
   const size_t M = (size_t)rs_msect_m(p);
   return (((size_t)RS_HDR + (size_t)RS_LD * (c + RS_PADR) + 7) & ~(size_t)7) + (size_t)c +
@@ -810,9 +825,7 @@ extern "C" hipError_t n2v2r_launch_rr_sturm(const double* hband, int c, int kp,
   // bisection writes wbis, the inverse iteration the refined values into theta
   {
     const unsigned grid = (unsigned)(pm * (M / nt_ms));
-    // rounds until the bracket is below 1e-10 ||H|| (3 at p = 80, M = 768; 4 at p = 160, M = 256)
-    int rounds = 1;
-    for (double wdt = 2.0 / ((double)pm * M + 1.0); wdt > 1e-10; wdt /= (double)(M + 1)) ++rounds;
+    const int rounds = rs_msect_rounds(pm, M);
     for (int r = 0; r < rounds; ++r) {
       hipLaunchKernelGGL(rr_msect_kernel<256>, dim3(grid), dim3(256), lms, stream, scr, c, kp, pm,
                          M, r, ms);

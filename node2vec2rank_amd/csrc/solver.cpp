@@ -33,10 +33,10 @@ namespace n2v2r_int {
 // from 4M nodes (round 6: the fused PIP pass past 64 KB of LDS; at cfg4's 1M nodes 768 columns
 // are no better -- 771 block applications against 788 on one graph, 846 against 788 on the
 // bench's --, at cfg5's 10M they are, see the kept-set rule below; profiles/r06_keep_basis.jsonl).
-// The reducing banded Rayleigh-Ritz keeps 640 (its arrow, chase and back-transform were never run
-// past 640 columns: the Sturm form's fallback beyond is the dense one on H expanded from the band).
+// The reducing banded Rayleigh-Ritz keeps 640 (kReduceMaxc, engine.h: its arrow, chase and
+// back-transform were never run past 640 columns: the Sturm form's fallback beyond is the dense
+// one on H expanded from the band).
 constexpr int kAutoMaxc = 640;
-constexpr int kReduceMaxc = 640;
 
 // The block / keep / basis rule of a fit: block width b, kept Ritz vectors at a restart and the
 // basis columns at most, from the wanted dimension d, the graph's N nodes and the caller's
@@ -111,17 +111,6 @@ BasisPlan plan_basis(int d, int64_t nglob, int block_opt, int keep_opt, int max_
   }
   return {b, keep, maxc};
 }
-
-// The form a cycle's Rayleigh-Ritz takes.  A cycle starts with Sturm, BandReduce (N2V2R_RR=b)
-// or Dense (no band kept) and moves only towards Dense: a failed Sturm result goes to
-// BandReduce, or past the reducing path's arrow to DenseFromBand; a failed BandReduce to Dense.
-enum class RrForm {
-  Sturm,          // banded: bisection + band inverse iteration on the saved band columns
-  BandReduce,     // banded: arrow reduction + bulge chase to a tridiagonal
-  DenseFromBand,  // dense steps on H expanded from the band columns
-  Dense           // dense steps on H = Q^T W
-};
-inline bool banded(RrForm f) { return f == RrForm::Sturm || f == RrForm::BandReduce; }
 
 // The cycle's pinned read-back [res | theta | flags[8] | R | S_last]: residuals and Ritz values
 // (keep doubles each), eight flag words, lean images' R (8 x 8 doubles) and the last 8 rows of S
@@ -662,7 +651,7 @@ struct Eig {
     // (kept sets past the reducing path's 192-row arrow, and bases past its 640 columns, take
     // the banded form only with the Sturm one, whose failure falls back to the dense
     // Rayleigh-Ritz on H expanded from the band)
-    band_reduce = keep + 8 <= 192 && c_max <= kReduceMaxc;
+    band_reduce = rr_reduce_fits(keep, c_max);
     band_rr = b == 8 && !flag(N2V2R_EIG_DENSE_RR) && c_max <= N2V2R_BAND_MAXC &&
               (band_reduce || rr_sturm_enabled());
     if (band_rr) {
@@ -1004,7 +993,8 @@ struct Eig {
       // a Sturm vector failed its residual check
       if (trace()) fprintf(stderr, "[n2v2r] Sturm Rayleigh-Ritz failed, reducing fallback\n");
       ++stats_rr_fallbacks;
-      if (!band_reduce) return RrForm::DenseFromBand;  // past the reducing path's arrow
+      const RrForm next = rr_after_sturm(keep, c_max);
+      if (next == RrForm::DenseFromBand) return next;  // past the reducing path's arrow
       // the kept Ritz values the reducing path reads: the copy the Sturm assembly made
       if (kry0 > 0)
         HIPCHK(hipMemcpyAsync(h->theta.as<double>(), h->ews.sturm.as<double>() + 4,
