@@ -341,8 +341,13 @@ extern "C" hipError_t n2v2r_launch_spmm(const SpmmArgs& args_in, int B, hipStrea
 
 // Packed flat windows: a wave owns windows of W = 2^wbits rows of the tile (32 at cfg4, 64 at
 // cfg5's sparser blocks); a window's entries in column block p are one contiguous run of the
-// block's index array (rows in order), located by two window offsets (scalar loads: the block
-// keeps no per-row pointers).  The wave walks the run 32 entries per step -- lane pair i takes
+// block's index array (rows in order), located by two window offsets (the block keeps no per-row
+// pointers).  The offsets and the phase's block record are wave-uniform and read through
+// constant-address-space pointers (uniform_const), so they are scalar loads: one s_load_dwordx2
+// per window into SGPRs.  (Until then they were per-lane global loads, each followed by
+// vmcnt(0) and readfirstlanes: 692.1 vs 684.9 us per cfg4 stage launch, 1,449.6-1,452.7 vs
+// 1,431.2-1,432.7 ms per step, profiles/spmm_scalar_prefetch_ab.jsonl.)
+// The wave walks the run 32 entries per step -- lane pair i takes
 // entry i, reads its packed word (row in window, column in block), gathers the 32-B panel row as
 // two 16-B halves and stages weight x row in a 1-KB per-wave LDS slot.  Then, per step, the first
 // lane pair of each row's segment (rows are in entry order and every entry names its row, so a
@@ -369,9 +374,14 @@ __device__ __forceinline__ const __attribute__((address_space(1))) T* uniform_gl
   return (const __attribute__((address_space(1))) T*)(((uint64_t)hi << 32) | lo);
 }
 
-__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
-  return ((int64_t)__builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32)) << 32) |
-         (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+// a wave-uniform pointer to memory that nothing writes during the launch (the block records and
+// window offsets, built at set-up), tagged as constant: loads through it at uniform addresses
+// are scalar loads -- the words arrive in SGPRs on lgkmcnt, without a per-lane load, a vmcnt(0)
+// wait and readfirstlanes.  (Through a plain global pointer the compiler must assume that the
+// kernel's own stores alias, and loads every uniform word per lane.)
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* uniform_const(const T* p) {
+  return (const __attribute__((address_space(4))) T*)(uint64_t)p;
 }
 
 // NS steps of 32 entries of one window run: index words and gathers of all NS steps issued as
@@ -515,6 +525,13 @@ __global__ __launch_bounds__(1024, 8) void spmm8_flat_kernel(SpmmTileArgs a) {
   // (0.448 ms); a wave owning one contiguous span of 4 windows walked as one run: 0.393 ms.
   // Round 5 (window offsets): two consecutive 64-row windows walked as one run, 0.351-0.356 vs
   // 0.351-0.353 ms, fit 1,441 vs 1,424 ms (profiles/r05_span2_ab.jsonl)
+  // Scalar offsets fetched ahead (same sums, profiles/spmm_scalar_prefetch_ab.jsonl; ms per
+  // cfg4 step): the next window's pair loaded while the current window is walked 1,433.5-1,437.0,
+  // carried over the barrier into the next phase as well 1,441.5-1,445.3, against 1,429.0-1,432.1
+  // with the pair loaded when its window starts (per-lane loads: 1,444.2-1,445.9).  The block
+  // record and all of a wave's offsets (consecutive windows per wave) held one phase ahead need
+  // 24 SGPRs beyond the 72 that 8 waves per SIMD allow: 33 SGPR spills, 1,446.9-1,450.9 against
+  // 1,430.1-1,433.3 (per-lane loads 1,450.5-1,452.6 in that session).
   for (int w = wave; w < nwin; w += nwave)
     for (int rr = pr; rr < W; rr += 32) {
       const int lr = (w << wbits) + rr;
@@ -523,14 +540,15 @@ __global__ __launch_bounds__(1024, 8) void spmm8_flat_kernel(SpmmTileArgs a) {
   for (int k = 0; k < a.K; ++k) {
     const float* X = a.X[k];
     for (int p = 0; p < a.nb; ++p) {
-      const CsrBlk& A = a.blk[k * a.nb + p];
-      const int cbits = __builtin_amdgcn_readfirstlane(A.cbits);
-      const int unit = __builtin_amdgcn_readfirstlane(A.unit);
-      const auto wo = uniform_global(A.wo);
+      // the phase's block record and, per window, its two offsets: scalar loads
+      const auto& A = uniform_const(a.blk)[k * a.nb + p];
+      const int cbits = A.cbits;
+      const int unit = A.unit;
+      const auto wo = uniform_const(A.wo);
       const auto ind = uniform_global(A.indices);
       const auto dat = uniform_global(A.data);
-      const int64_t base = uniform_i64(A.base);
-      const int64_t col0 = uniform_i64(A.col0);
+      const int64_t base = A.base;
+      const int64_t col0 = A.col0;
       const int32_t cmask = (1 << cbits) - 1;
       const auto Xb = uniform_global(X + col0 * a.ldx);
       for (int w = wave; w < nwin; w += nwave) {
