@@ -219,6 +219,44 @@ int n2v2r_rr_stage(n2v2r_handle* h, int c, int kp, const double* hband, int64_t 
                    const double* theta_prev, int p, int form, double* w, float* S,
                    double* Y /* optional, c x p */, n2v2r_rr_info* info);
 
+/* What one n2v2r_embed_step launched, from the launchers' own shape rules. */
+typedef struct n2v2r_embed_info {
+  int form;      /* the products' form in the n2v2r_eig_stats.spmm_form codes: 0 the CSR row kernels
+                    (also on a handle whose applications take the XCD split: the embedding's
+                    products never do), 4 dense, 5 tiled (-1: the call was refused) */
+  int launches;  /* product launches: ldu / b row-kernel launches over all K layers, ldu / 8 tiled
+                    launches over all K layers, K * ldu / 64 dense GEMMs */
+  int ldu;       /* row stride of U and of every Y_k: 64 * ceil(d / 64) */
+  int rpw;       /* row-kernel form: rows per wave of the last launch (the launcher's rule on the
+                    arguments launched), else 0 */
+  int64_t colmax_chunks; /* row chunks of the column-max pass over this handle's local rows */
+  int64_t colmax_rows;   /* rows per chunk (the last chunk may be shorter) */
+} n2v2r_embed_info;
+
+/* The step that turns a converged fit into the embedding alone (tests), through the solver's own
+ * build_embedding with a GramOp set up as a fit's at block width b (8, 16, 32 or 64): the sign
+ * pass (every column of U flipped so that its entry of largest magnitude, the smallest global row
+ * on ties, is positive; +1 for a zero entry), sigma = sqrt(max(theta, 0)) and Y_k = A_k^T U
+ * sigma^(-1/2) (a zero column where sigma is 0) in whichever form a fit at this width would take
+ * on this handle under the environment switches in force: the row kernels on strided panels, the
+ * tiled SpMM on 8-column slices, the dense GEMMs; on a rank handle the same on the all-gathered
+ * U, with the sign keys and signs all-reduced.  The products the final lean check of a fit may
+ * have captured are not reachable through this entry.
+ * U: the global N x d fp32 matrix, row-major (a rank handle uploads its own rows: the call is
+ * collective, every rank makes it with the same U); theta: d fp64 Ritz values.  The rows go into
+ * the handle's U at row stride ldu, padded rows and columns zeroed first, as n2v2r_uase zeroes
+ * them.  The local rows of every Y_k, the column scales, the chunk keys and the winning keys are
+ * filled with NaN bytes before the step, so what no launch wrote shows.  The result is installed
+ * as the handle's embedding exactly as a fit installs it (U, Y, sigma, d, the row stride; the
+ * ranking results cleared): read it with n2v2r_get_embedding, n2v2r_get_left_embedding and
+ * n2v2r_get_singular_values.  info (optional): what ran.  A later fit is bit-identical to one
+ * without the call.
+ * N2V2R_ERR_BAD_ARG on a multi-GPU parent handle (its ranks would each need the call), without
+ * loaded layers, for another b, for d outside [1, min(600, n - 1)] and for a NULL U or theta; the
+ * handle's embedding and ranking results are then left alone. */
+int n2v2r_embed_step(n2v2r_handle* h, int b, int d, const float* U, const double* theta,
+                     n2v2r_embed_info* info);
+
 /* Layer bytes each rank copied host -> device so far (one-GPU handle: one entry): row pointers,
  * column indices and values of every CSR layer ingest and the 8 n samples bytes of every
  * n2v2r_set_layer_corr (each rank uploads E whole), into per_rank[0 .. min(W, cap)).  Returns the

@@ -59,7 +59,7 @@ EXPORTED = [
     "n2v2r_block_gram", "n2v2r_ortho_pass", "n2v2r_soft_connectivity",
     "n2v2r_soft_connectivity_chunks", "n2v2r_set_layer_corr_method",
     "n2v2r_soft_connectivity_method", "n2v2r_corr_ranks", "n2v2r_corr_standardise",
-    "n2v2r_bench_corr_rows", "n2v2r_rr_stage",
+    "n2v2r_bench_corr_rows", "n2v2r_rr_stage", "n2v2r_embed_step",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -100,6 +100,12 @@ class EigStats(ctypes.Structure):
 class GramInfo(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int) for k in ("form", "rs_form", "rs_chunks", "split2", "tile_nb",
                                             "tile_wb", "tile_rows", "rpw1", "rpw2")]
+
+
+class EmbedInfo(ctypes.Structure):
+    _fields_ = [("form", ctypes.c_int), ("launches", ctypes.c_int), ("ldu", ctypes.c_int),
+                ("rpw", ctypes.c_int), ("colmax_chunks", ctypes.c_int64),
+                ("colmax_rows", ctypes.c_int64)]
 
 
 class RitzInfo(ctypes.Structure):
@@ -209,6 +215,7 @@ def load(path: str | None = None):
                                     _p(np.int32), _p(np.int32), _p(np.int32)]),
             "n2v2r_gram_apply": (_i, [_vp, _i, _p(np.float32), _vp, _p(np.float32),
                                       ctypes.POINTER(GramInfo)]),
+            "n2v2r_embed_step": (_i, [_vp, _i, _i, _vp, _vp, ctypes.POINTER(EmbedInfo)]),
             "n2v2r_ritz_step": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(RitzInfo)]),
             "n2v2r_block_gram": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, ctypes.POINTER(PassInfo)]),
@@ -1006,6 +1013,27 @@ class Engine:
             self.h, int(b), X, Z.ctypes.data_as(ctypes.c_void_p) if want_z else None, W,
             ctypes.byref(info)), "gram_apply")
         return W, Z, {k: getattr(info, k) for k, _ in GramInfo._fields_}
+
+    def embed_step(self, U, theta, b: int = 8):
+        """The step from a converged fit's left vectors to the embedding alone (see
+        n2v2r_embed_step): signs, sigma = sqrt(theta) and Y_k = A_k^T U sigma^(-1/2) in the form a
+        fit at block width b takes on this handle.  U: the global (N, d) fp32 matrix (on a rank
+        handle every rank calls with the same U); theta: d fp64.  The result is installed as the
+        handle's embedding: read it with embedding(), left_embedding() and singular_values().
+        Returns a dict of n2v2r_embed_info's fields."""
+        if U is None or theta is None:
+            raise ValueError("embed_step: U and theta are required")
+        U = np.ascontiguousarray(U, dtype=np.float32)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if U.ndim != 2 or U.shape[0] != self.n or theta.shape != (U.shape[1],):
+            raise ValueError(f"embed_step: U must be ({self.n}, d) and theta (d,), got "
+                             f"{U.shape} and {theta.shape}")
+        info = EmbedInfo()
+        self._check(self.lib.n2v2r_embed_step(
+            self.h, int(b), int(U.shape[1]), U.ctypes.data_as(ctypes.c_void_p),
+            theta.ctypes.data_as(ctypes.c_void_p), ctypes.byref(info)), "embed_step")
+        self.d = int(U.shape[1])
+        return {k: getattr(info, k) for k, _ in EmbedInfo._fields_}
 
     def ritz_step(self, Q, W, S, theta, lean: bool = False):
         """The step between Rayleigh-Ritz and the next cycle alone (see n2v2r_ritz_step).  Q, W:

@@ -2650,10 +2650,10 @@ __global__ void colmax_sign_kernel(const unsigned long long* __restrict__ best, 
   sign[col] = sgn;
 }
 
-extern "C" hipError_t n2v2r_launch_colmax_keys(const float* U, int64_t ldu, int64_t n, int d,
-                                               int64_t row0, unsigned long long* keys,
-                                               size_t key_elems, unsigned long long* best,
-                                               hipStream_t stream) {
+// The row chunks of the column-max pass over n rows and d columns with room for key_elems keys
+// (one per chunk and column of the 32-column tiles): the launcher's own rule.
+extern "C" hipError_t n2v2r_colmax_plan(int64_t n, int d, size_t key_elems, int64_t* nchunks_out,
+                                        int64_t* rows_per_chunk) {
   const int tiles = (d + 31) / 32;
   // ~256 rows per chunk (cfg2: 391 x 2 workgroups; 4096-row chunks kept 50 CUs busy, 139 us)
   int64_t nchunks = (n + 255) / 256;
@@ -2665,9 +2665,22 @@ extern "C" hipError_t n2v2r_launch_colmax_keys(const float* U, int64_t ldu, int6
   if (rows < 1) rows = 1;
   nchunks = (n + rows - 1) / rows;
   if (nchunks < 1) nchunks = 1;
+  *nchunks_out = nchunks;
+  *rows_per_chunk = rows;
+  return hipSuccess;
+}
+
+extern "C" hipError_t n2v2r_launch_colmax_keys(const float* U, int64_t ldu, int64_t n, int d,
+                                               int64_t row0, unsigned long long* keys,
+                                               size_t key_elems, unsigned long long* best,
+                                               hipStream_t stream) {
+  const int tiles = (d + 31) / 32;
+  int64_t nchunks = 0, rows = 0;
+  hipError_t e = n2v2r_colmax_plan(n, d, key_elems, &nchunks, &rows);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(colmax_partial_kernel, dim3((unsigned)nchunks, tiles), dim3(256), 0, stream,
                      U, ldu, n, d, rows, row0, keys);
-  hipError_t e = hipGetLastError();
+  e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(colmax_fold_kernel, dim3((tiles * 32 + 3) / 4), dim3(256), 0, stream,
                      keys, (int)nchunks, tiles * 32, best);

@@ -87,6 +87,9 @@ hipError_t n2v2r_launch_resid(const BlockList& X, const BlockList& MX, const dou
                               hipStream_t stream);
 hipError_t n2v2r_launch_scale_cols(float* blk, int w, int64_t n, const float* s,
                                    hipStream_t stream);
+// the row chunks n2v2r_launch_colmax_keys takes at this shape (the launcher calls it)
+hipError_t n2v2r_colmax_plan(int64_t n, int d, size_t key_elems, int64_t* nchunks,
+                             int64_t* rows_per_chunk);
 hipError_t n2v2r_launch_colmax_keys(const float* U, int64_t ldu, int64_t n, int d, int64_t row0,
                                     unsigned long long* keys, size_t key_elems,
                                     unsigned long long* best, hipStream_t stream);

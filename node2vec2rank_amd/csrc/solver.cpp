@@ -1335,11 +1335,18 @@ void copy_embedding(n2v2r_handle* h, float* Y, int64_t layer_stride) {
 // The embedding of a finished fit from its left vectors U (h->U, ld ldu) and Ritz values theta:
 // deterministic signs, sigma = sqrt(theta), and Y_k = A_k^T U sigma^(-1/2) into h->Y -- the
 // products the final lean check captured (`captured`), the fit's tiled SpMM, or the row kernel /
-// the dense GEMM.
+// the dense GEMM.  info (n2v2r_embed_step): what was launched, by the launchers' own rules.
 static void build_embedding(n2v2r_handle* h, const GramOp& op, const std::vector<double>& theta,
-                            int ldu, bool captured) {
+                            int ldu, bool captured, n2v2r_embed_info* info = nullptr) {
   const int d = (int)theta.size(), b = op.b;
   const bool tiled = op.col_blocks;  // (b = 8 then)
+  if (info) {
+    *info = n2v2r_embed_info{};
+    info->form = h->dense_layers() ? 4 : tiled ? 5 : 0;
+    info->ldu = ldu;
+    HIPCHK(n2v2r_colmax_plan(h->nloc, d, 1024 * (size_t)ldu, &info->colmax_chunks,
+                             &info->colmax_rows));
+  }
   // deterministic signs: largest-magnitude entry of every column of U positive
   h->keys.ensure(sizeof(unsigned long long) * 1024 * (size_t)ldu);
   h->best.ensure(sizeof(unsigned long long) * ldu);
@@ -1391,6 +1398,7 @@ static void build_embedding(n2v2r_handle* h, const GramOp& op, const std::vector
         h->dense_apply(L.dense_at(), L.lda, ug + q * 64, ldu, std::min(64, ldu - q * 64),
                        h->Y.as<float>() + (size_t)k * h->npad * ldu + q * 64, ldu, 0.f,
                        h->colscale.as<float>() + q * 64);
+      if (info) info->launches += (ldu + 63) / 64;
     }
   }
   if (!h->dense_layers() && tiled) {
@@ -1409,6 +1417,7 @@ static void build_embedding(n2v2r_handle* h, const GramOp& op, const std::vector
         a.Y[k] = h->Y.as<float>() + (size_t)k * h->npad * ldu + q * 8;
       }
       HIPCHK(n2v2r_launch_spmm_tile(a, h->stream));
+      if (info) ++info->launches;
     }
     for (int k = 0; k < h->K; ++k)
       HIPCHK(n2v2r_launch_scale_cols(h->Y.as<float>() + (size_t)k * h->npad * ldu, ldu,
@@ -1428,6 +1437,10 @@ static void build_embedding(n2v2r_handle* h, const GramOp& op, const std::vector
       a.Y[k] = h->Y.as<float>() + (size_t)k * h->npad * ldu + q * b;
     }
     HIPCHK(n2v2r_launch_spmm(a, b, h->stream));
+    if (info) {
+      ++info->launches;
+      info->rpw = n2v2r_spmm_rpw(a, b);
+    }
   }
   HIPCHK(hipStreamSynchronize(h->stream));
 }
@@ -1486,6 +1499,56 @@ int n2v2r_uase(n2v2r_handle* h, int d, const n2v2r_eig_opts* opts, n2v2r_eig_sta
                  stats ? stats->max_residual : -1.0, o.tol > 0 ? o.tol : 1e-6,
                  stats && stats->stagnated ? "; stopped flat above the fp32-floor cap" : "");
     return st;
+  });
+}
+
+// The embedding step alone (tests): a GramOp set up as a fit's at width b, build_embedding on a
+// host U and theta, the result installed as a fit installs it.
+int n2v2r_embed_step(n2v2r_handle* h, int b, int d, const float* U, const double* theta,
+                     n2v2r_embed_info* info) {
+  if (info) {
+    *info = n2v2r_embed_info{};
+    info->form = -1;
+  }
+  return guarded(h, [&]() -> int {
+    if (h->multi() || (b != 8 && b != 16 && b != 32 && b != 64) || !U || !theta)
+      return N2V2R_ERR_BAD_ARG;
+    if (!layers_ready(h)) return N2V2R_ERR_BAD_ARG;
+    if (d < 1 || d > 600 || d >= h->n) {
+      h->set_err("embedding dimension %d out of range [1, min(600, n-1)]", d);
+      return N2V2R_ERR_BAD_ARG;
+    }
+    GramOp op(h);
+    op.setup(b);
+    hipStream_t st = h->stream;
+    // as n2v2r_uase: no stale embedding or ranking results readable from here on
+    h->have_embedding = false;
+    h->ncmp = h->ncols = 0;
+    h->have_borda = false;
+    const int ldu = ((d + 63) / 64) * 64;
+    h->U.ensure(sizeof(float) * h->npad * ldu);
+    HIPCHK(hipMemsetAsync(h->U.p, 0, sizeof(float) * h->npad * ldu, st));
+    if (h->nloc > 0)
+      HIPCHK(hipMemcpy2DAsync(h->U.p, sizeof(float) * ldu, U + (size_t)h->row0 * d,
+                              sizeof(float) * d, sizeof(float) * d, h->nloc,
+                              hipMemcpyHostToDevice, st));
+    // NaN bytes wherever the step has to write (the sizes are build_embedding's own): the local
+    // rows of every Y_k, the column scales, the chunk keys and the winning keys
+    h->keys.ensure(sizeof(unsigned long long) * 1024 * (size_t)ldu);
+    h->best.ensure(sizeof(unsigned long long) * ldu);
+    h->colscale.ensure(sizeof(float) * ldu);
+    h->Y.ensure(sizeof(float) * (size_t)h->K * h->npad * ldu);
+    HIPCHK(hipMemsetAsync(h->keys.p, 0xFF, sizeof(unsigned long long) * 1024 * (size_t)ldu, st));
+    HIPCHK(hipMemsetAsync(h->best.p, 0xFF, sizeof(unsigned long long) * ldu, st));
+    HIPCHK(hipMemsetAsync(h->colscale.p, 0xFF, sizeof(float) * ldu, st));
+    for (int k = 0; k < h->K && h->nloc > 0; ++k)
+      HIPCHK(hipMemsetAsync(h->Y.as<float>() + (size_t)k * h->npad * ldu, 0xFF,
+                            sizeof(float) * h->nloc * ldu, st));
+    HIPCHK(hipStreamSynchronize(st));  // pageable source: complete before the kernels
+    build_embedding(h, op, std::vector<double>(theta, theta + d), ldu, false, info);
+    h->have_embedding = true;
+    h->ncmp = h->ncols = 0;
+    return N2V2R_OK;
   });
 }
 
