@@ -383,6 +383,7 @@ int n2v2r_rank_timing(n2v2r_handle* h, double* ms_distances, double* ms_borda);
 /* host-array seams */
 int n2v2r_pairwise_distances(n2v2r_handle* h, const double* m1, const double* m2, int64_t n,
                              int dim, int metric, double* out);
+/* n <= 2^31 - 1 (N2V2R_ERR_BAD_ARG otherwise, before D is read). */
 int n2v2r_borda_columns(n2v2r_handle* h, const double* D /* C*N column-major */, int64_t n,
                         int n_cols, int64_t* borda);
 /* Row sums of the stored A^T (of A when symmetric); an unweighted layer's entries count 1.0f each:

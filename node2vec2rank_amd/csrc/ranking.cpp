@@ -219,7 +219,8 @@ int n2v2r_pairwise_distances(n2v2r_handle* h, const double* m1, const double* m2
 int n2v2r_borda_columns(n2v2r_handle* h, const double* D, int64_t n, int n_cols, int64_t* borda) {
   if (h && h->multi()) h = h->ranks[0];
   return guarded(h, [&]() -> int {
-    if (n < 1 || n_cols < 1 || !D || !borda) return N2V2R_ERR_BAD_ARG;
+    // the sort's payload (row index) is int32, as in n2v2r_borda_columns_ex
+    if (n < 1 || n_cols < 1 || !D || !borda || n > INT32_MAX) return N2V2R_ERR_BAD_ARG;
     DevBuf dd, bo;
     dd.ensure(sizeof(double) * n * n_cols);
     bo.ensure(sizeof(int64_t) * n);
